@@ -12,6 +12,10 @@ Synthetic seeded weights / prompt embeddings (no checkpoints on the box), inputs
 Prints ONE JSON line (rank 0).  Launch for N > 1:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline (metric, value, unit, ms_per_step, ...).  Everything
+else it can measure -- the serial leg and its per-kernel roofline, clock and power, the epoch leg, the pricing legs of the other
+modes, the scaling diagnostics, the CPU baseline -- runs with --full.  --dump-outputs DIR writes what the last timed step computed.
 """
 import argparse
 import json
@@ -35,6 +39,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the serial leg + per-kernel roofline, clock and power, the epoch leg, the pricing legs, "
+                         "the scaling diagnostics (N > 1) and the CPU baseline; --no-epoch / --no-pricing / --no-cpu-baseline trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (images, latents, log-probs, timesteps, rewards, "
+                         "advantages of rank 0's prompt group) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-only", action="store_true")
     ap.add_argument("--no-epoch", action="store_true", help="skip the untimed-for-the-metric full-epoch leg")
@@ -455,6 +465,30 @@ def scaling_diagnostics(dist, device, world, rank, G, T, dt_local, dt_max, steps
                     "HIP events around back-to-back calls"}
 
 
+DUMP_LIMIT_BYTES = 60_000_000       # (+ the .npy headers: under 64 MB)
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every tensor of `arrays` as <outdir>/<name>.npy, float32 (float64 stays float64), at most DUMP_LIMIT_BYTES in all.
+    Smallest first; an array larger than its share of what is left is written as a fixed sample of its flattened elements, drawn by a
+    generator seeded from its name and shape alone, so that two builds of the project sample the same elements."""
+    import zlib
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {k: v.detach().to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy() for k, v in arrays.items()}
+    left = DUMP_LIMIT_BYTES
+    for i, (name, a) in enumerate(sorted(host.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(host) - i)
+        if a.nbytes > share:
+            k = share // a.itemsize
+            rng = np.random.default_rng(zlib.crc32(f"{name}{a.shape}".encode()))
+            idx = np.sort(rng.choice(a.size, size=k, replace=False))
+            print(f"bench.py: {name} {a.shape} is written as a seeded sample of {k} of its {a.size} elements", file=sys.stderr)
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, f"{name}.npy"), a)
+        left -= a.nbytes
+
+
 def host_rss_mb():
     import resource
     return round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0, 1)        # (Linux: kilobytes)
@@ -594,7 +628,7 @@ def main():
                               for t in synthetic.prompt_embeddings(7 + rank, n_tokens=C5_TEXT_TOKENS, ctx_dim=3584, pooled_dim=8))
         if rank == 0 and not args.no_pricing:
             # the prompt encoder itself (Qwen2.5-VL language model, 28 layers, random weights), OUTSIDE the timed region as for every
-            # config (inputs are resident when the step starts): its states replace the random ones, its time is reported
+            # config (inputs are resident when the step starts): its states replace the random ones, its time is reported (--full)
             from adv_grpo_amd.model_configs import QwenTextConfig
             from adv_grpo_amd.qwen_text_encoder import DROP_IDX, Qwen25VLTextEncoder
             tcfg = QwenTextConfig()
@@ -602,15 +636,16 @@ def main():
                 enc = Qwen25VLTextEncoder(synthetic.qwen_text_weights(tcfg, 1357, dtype=torch.bfloat16), tcfg, device)
             tok = torch.randint(0, tcfg.vocab_size, (2, DROP_IDX + C5_TEXT_TOKENS), generator=torch.Generator().manual_seed(11)).to(device)
             tmask = torch.ones(2, DROP_IDX + C5_TEXT_TOKENS, dtype=torch.long)
-            enc.encode_prompt(tok, tmask)
-            torch.cuda.synchronize()
-            tt = time.perf_counter()
-            for _ in range(3):
-                emb, _m = enc.encode_prompt(tok, tmask)
-            torch.cuda.synchronize()
-            text_tower = {"ms_per_prompt_pair": round((time.perf_counter() - tt) / 3 * 1e3, 2), "tokens": DROP_IDX + C5_TEXT_TOKENS,
-                          "note": "Qwen2.5-VL language model (28 layers, 3584 wide, random weights) on (prompt, negative prompt) token ids "
-                                  "after the chat template; the first 34 template tokens dropped; outside the timed step"}
+            emb, _m = enc.encode_prompt(tok, tmask)
+            if args.full:
+                torch.cuda.synchronize()
+                tt = time.perf_counter()
+                for _ in range(3):
+                    emb, _m = enc.encode_prompt(tok, tmask)
+                torch.cuda.synchronize()
+                text_tower = {"ms_per_prompt_pair": round((time.perf_counter() - tt) / 3 * 1e3, 2), "tokens": DROP_IDX + C5_TEXT_TOKENS,
+                              "note": "Qwen2.5-VL language model (28 layers, 3584 wide, random weights) on (prompt, negative prompt) token ids "
+                                      "after the chat template; the first 34 template tokens dropped; outside the timed step"}
             pe, npe = emb[:1].contiguous(), emb[1:].contiguous()
             del enc, emb
             torch.cuda.empty_cache()
@@ -643,10 +678,15 @@ def main():
         sampler.set_epoch(it)
         return next(iter(sampler))[0]
 
+    # --dump-outputs: the group of the last timed step keeps what the rollout returned and its scores, until they are written
+    dump = {"it": args.warmup + args.steps - 1 if args.dump_outputs else None, "out": {}}
+
     def rollout_and_submit(it, worker=None, prompt_idx=None):
         """Rollout (+ decode) of one prompt group on the current stream; its scoring on `worker` (None: the current stream)."""
         if prompt_idx is None:
             prompt_idx = prompt_of(it)
+        keep = (lambda image, scores: dump["out"].update(images=image, latents=lats, log_probs=lps, timesteps=tss, rewards=scores)
+                ) if it == dump["it"] else None
         image, lats, lps, tss = pipeline_with_logprob_random(
             pipe, prompt_embeds=pe, pooled_prompt_embeds=ppe, negative_prompt_embeds=npe,
             negative_pooled_prompt_embeds=nppe, num_inference_steps=STEPS, guidance_scale=4.5,
@@ -655,7 +695,10 @@ def main():
             output_type="latent" if (worker is not None and args.decode_in_future) else "pt")
         if worker is None:
             with score_lock:
-                return prompt_idx, lps, score(image), None
+                scores = score(image)
+            if keep:
+                keep(image, scores)
+            return prompt_idx, lps, scores, None
         ready = torch.cuda.Event()
         ready.record()
         with score_lock, torch.cuda.stream(worker):
@@ -669,6 +712,8 @@ def main():
             done.record(worker)
         if not args.decode_in_future:
             image.record_stream(worker)
+        if keep:
+            keep(image, scores)
         return prompt_idx, lps, scores, done
 
     def finish(pending, exchange=True):
@@ -764,9 +809,11 @@ def main():
         pipe.vae.two_streams = False
     if args.warmup:
         timed_steps(0, args.warmup)
-    ops.PROFILE, ops.PROFILE_STRIDE = ([] if in_flight == 1 else None), max(1, args.event_stride)
+    # (--full: HIP events around every event_stride-th GEMM launch of the serial schedule's timed steps, and the rocm-smi sampler beside them)
+    ops.PROFILE, ops.PROFILE_STRIDE = ([] if in_flight == 1 and args.full else None), max(1, args.event_stride)
     sync()
-    with PowerSampler(local_rank if rank == 0 and os.environ.get("ADVGRPO_BENCH_NO_SMI", "0") != "1" else -1) as power:
+    sample_power = args.full and rank == 0 and os.environ.get("ADVGRPO_BENCH_NO_SMI", "0") != "1"
+    with PowerSampler(local_rank if sample_power else -1) as power:
         t0 = time.perf_counter()
         if args.rollout_priority:
             hp = torch.cuda.Stream(device=device, priority=args.rollout_priority)
@@ -782,6 +829,76 @@ def main():
     assert torch.isfinite(out[0]).all() and torch.isfinite(out[1]).all()
     if vae_split is not None and not args.vae_one_stream:
         pipe.vae.two_streams = vae_split
+    dt_local = dt
+    if dist is not None:                            # the headline is the slowest rank's time
+        tmax = torch.tensor([dt], dtype=torch.float64, device=device)
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        dt = tmax.item()
+    if dump["it"] is not None:
+        if rank == 0:
+            o = dump["out"]
+            dump_outputs(args.dump_outputs, {"images": o["images"], "latents": torch.stack(o["latents"], 1), "log_probs": torch.stack(o["log_probs"], 1),
+                                             "timesteps": torch.stack(o["timesteps"], 1), "rewards": o["rewards"], "advantages": out[0]})
+        dump["it"] = None
+        dump["out"].clear()
+
+    images = world * G * args.steps
+    # algorithmic FLOPs per sampled+scored image: 10*2*2.219 + 2.51 + 0.38 TFLOP at config 2;
+    # SD3.5-large 1024^2 (config 4 shapes): 30.02 TFLOP per sample-forward, VAE x4 pixels
+    per_image_tflop = (10 * 2 * 30.02 + 4 * 2.51 + 0.38) if c4 else (10 * 2 * 2.219 + 2.51 + (0.30 if c3 else 0.38))
+    mixed_peak_s = None
+    if c5:      # Qwen-Image at 1024^2: 4096 packed positions + the text tokens; Linears on the fp8 MFMA, attention / VAE / DINO on bf16
+        from adv_grpo_amd.qwen_mmdit import flops_per_sample_forward
+        qc, n_img = pipe.transformer.cfg, (RES // 16) ** 2
+        f_fwd = flops_per_sample_forward(qc, n_img, C5_TEXT_TOKENS) / 1e12
+        f_attn = 4.0 * qc.dim * (n_img + C5_TEXT_TOKENS) ** 2 * qc.num_layers / 1e12
+        from adv_grpo_amd.qwen_vae import flops_decode
+        f_vae = flops_decode(pipe.vae.cfg, RES // 8, RES // 8) / 1e12        # Qwen-Image's own decoder on one frame: 4.71 TFLOP at 1024^2
+        per_image_tflop = 10 * 2 * f_fwd + f_vae + 0.30
+        # seconds per image at the peaks of the units the work runs on: what "1.0 of the roofline" would be for this mix
+        mixed_peak_s = (10 * 2 * (f_fwd - f_attn)) / FP8_DENSE_PEAK_TFLOPS + (10 * 2 * f_attn + f_vae + 0.30) / BF16_DENSE_PEAK_TFLOPS
+    vae_ran = pipe.vae.arithmetic()["text"] if hasattr(pipe.vae, "arithmetic") else pipe.vae.mode
+    headline = {
+        "metric": "sampled+scored images/sec (whole node), SD3.5-large 1024^2 10-step G=4 (secondary line, BASELINE config 4 shapes)"
+        if c4 else ("sampled+scored images/sec (whole node), Qwen-Image MMDiT 1024^2 10-step G=8, DINO reward, fp8 Linears (secondary line, "
+                    "BASELINE config 5 shapes)" if c5 else ("sampled+scored images/sec (whole node), SD3-med 512^2 10-step G=8, DINOv2-patch "
+                    "adversarial reward (BASELINE config 3, rank-local work)" if c3 else "sampled+scored images/sec (whole node), SD3-med 512^2 10-step G=8 GRPO")),
+        "value": round(images / dt, 3), "unit": "images/s", "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "fp8" if c5 else "bf16", "data": "synthetic",
+        "config": {"workload": ("BASELINE config 5 shapes: Qwen-Image MMDiT (60 blocks, 24 heads x 128, D=3072; block Linears on fp8 e4m3 operands, "
+                                "per-token x per-channel scales, f32 accumulation; attention / norms / embedders bf16) 1024x1024 = 4096 packed "
+                                f"latent positions + {C5_TEXT_TOKENS} text tokens (3584-wide states of the Qwen2.5-VL text tower on synthetic token ids), 10 steps, CFG 4.5 as u + s (t - u) "
+                                "(the rollout function's combine, PF:640-642, not QwenImagePipeline's norm-rescaled one), G=8, SDE window 2 @ noise 0.8 on "
+                                "the SD3 sigma table (shift 3), VAE decode (" + pipe.vae.mode + ") with Qwen-Image's own decoder (AutoencoderKLQwenImage on one "
+                                "frame: widths 384 / 192 / 96, per-pixel RMS norm), DINOv2-B/14 patch reward + head (RW:375-434), reward all-gather + group advantage")
+                               if c5 else (("BASELINE config 4 shapes: SD3.5-large (38 blocks, D=2432) LoRA-merged 1024x1024, 10 steps, CFG 4.5, "
+                                "G=4, SDE window 2 @ noise 0.8, VAE decode (fp32-equivalent; 3x3 convolutions: " + vae_ran + "), fp32-equivalent PickScore reward (ocr: stand-in "
+                                "recogniser -- no PaddleOCR in this image, the OCR half of the reward is a constant and its host-side recognition costs nothing here), "
+                                "reward all-gather + group advantage") if c4 else
+                               ("BASELINE config " + ("3" if c3 else "2") + ": SD3.5-medium LoRA-merged 512x512, 10 steps, CFG 4.5, G=8, "
+                                "SDE window 2 @ noise 0.8, VAE decode (fp32-equivalent; 3x3 convolutions: " + vae_ran + "), " +
+                                ("co-trained DINOv2 ViT-B/14 @ 518 patch discriminator + head as reward (RW:375-434)" if c3 else
+                                 "PickScore (CLIP ViT-H/14) reward") + ", reward all-gather + group advantage")), "global_batch": world * G,
+                   "transformer_batch_per_gpu": 2 * G, "parallelism": f"dp{world} (prompt groups sharded)",
+                   "schedule": ("trainer default (config sample.groups_in_flight = 2, adv_grpo_amd/trainer.py sample_epoch): two prompt groups per rank rolled "
+                                "out at the same time, one HIP stream + one host thread each (a group's VAE decode on that one stream), scores as reward futures on one scoring stream, "
+                                "reward gather + group advantage per group on the main thread in group order; samples bit-identical to the serial "
+                                "schedule (tests/test_gpu_trainer.py::test_groups_in_flight_do_not_change_the_samples)")
+                   if in_flight > 1 else "serial: one prompt group at a time on the launch stream, scores as reward futures"},
+        "effective_tflops_per_gpu": round(per_image_tflop * images / dt / world, 1),
+        "frac_of_bf16_mfma_peak": round(per_image_tflop * images / dt / world / BF16_DENSE_PEAK_TFLOPS, 4),
+        **({"frac_of_mixed_mfma_peak": round(mixed_peak_s * images / dt / world, 4),
+            "mixed_peak_is": "Linear FLOPs priced at the dense fp8 peak (5 PFLOP/s), attention / VAE / DINO FLOPs at the dense bf16 peak (2.5 PFLOP/s): "
+                             "time at those peaks / measured time"} if c5 else {}),
+    }
+    if not args.full:                               # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(headline))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     # The serial leg (trainer schedule only): the same number of steps, one prompt group at a time on the launch stream.  Per-kernel
     # durations are only defined here -- with two groups in flight a launch's HIP-event interval includes the other stream's kernels -- so
     # the `roofline` object is taken from this leg and `serial` carries its whole-step figures.  Every rank runs it (it has the collectives).
@@ -802,10 +919,6 @@ def main():
             serial_dt = tmax_s.item()
     scaling_diag = None
     if dist is not None:
-        dt_local = dt
-        tmax = torch.tensor([dt], dtype=torch.float64, device=device)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        dt = tmax.item()
         scaling_diag = scaling_diagnostics(dist, device, world, rank, G, T, dt_local, dt, args.steps, step, D)
 
     # The epoch leg runs HERE, right behind the timed steps, for every configuration whose two model sets fit one GPU side by side (all but
@@ -838,21 +951,6 @@ def main():
                             "steps, one prompt group at a time): with two groups in flight a launch's event interval includes the other stream's "
                             "kernels, so per-kernel durations are only defined on the serial schedule; share_of_step_time is of the serial step")
                            if serial_dt else "HIP events on the launch stream around every event_stride-th launch of the kernel inside the timed steps"}
-        images = world * G * args.steps
-        # algorithmic FLOPs per sampled+scored image: 10*2*2.219 + 2.51 + 0.38 TFLOP at config 2;
-        # SD3.5-large 1024^2 (config 4 shapes): 30.02 TFLOP per sample-forward, VAE x4 pixels
-        per_image_tflop = (10 * 2 * 30.02 + 4 * 2.51 + 0.38) if c4 else (10 * 2 * 2.219 + 2.51 + (0.30 if c3 else 0.38))
-        mixed_peak_s = None
-        if c5:      # Qwen-Image at 1024^2: 4096 packed positions + the text tokens; Linears on the fp8 MFMA, attention / VAE / DINO on bf16
-            from adv_grpo_amd.qwen_mmdit import flops_per_sample_forward
-            qc, n_img = pipe.transformer.cfg, (RES // 16) ** 2
-            f_fwd = flops_per_sample_forward(qc, n_img, C5_TEXT_TOKENS) / 1e12
-            f_attn = 4.0 * qc.dim * (n_img + C5_TEXT_TOKENS) ** 2 * qc.num_layers / 1e12
-            from adv_grpo_amd.qwen_vae import flops_decode
-            f_vae = flops_decode(pipe.vae.cfg, RES // 8, RES // 8) / 1e12        # Qwen-Image's own decoder on one frame: 4.71 TFLOP at 1024^2
-            per_image_tflop = 10 * 2 * f_fwd + f_vae + 0.30
-            # seconds per image at the peaks of the units the work runs on: what "1.0 of the roofline" would be for this mix
-            mixed_peak_s = (10 * 2 * (f_fwd - f_attn)) / FP8_DENSE_PEAK_TFLOPS + (10 * 2 * f_attn + f_vae + 0.30) / BF16_DENSE_PEAK_TFLOPS
         # the decoder on its own (bf16 MFMA / f32 accumulate; the reference decodes in fp32, TP:481 -- DESIGN 3 deviation 1)
         # and the fp32-equivalent split-bf16 mode (3 bf16 MFMA products per f32 product, f32 between the kernels) beside it
         from adv_grpo_amd import synthetic
@@ -895,7 +993,6 @@ def main():
             torch.cuda.synchronize()
             vae_ms["f16x1"] = (time.perf_counter() - tv) / 3 * 1e3
             del dec
-        vae_ran = pipe.vae.arithmetic()["text"] if hasattr(pipe.vae, "arithmetic") else pipe.vae.mode
         if not c5 and pipe.vae.mode == "bf16x3" and not args.no_pricing:
             with synthetic.on_device(device):
                 dec = AutoencoderKLDecoder(synthetic.vae_decoder_weights(pipe.vae.cfg, 4321, fp16_checkpoint=False), pipe.vae.cfg, device, mode="bf16x3")
@@ -1030,38 +1127,7 @@ def main():
                                                            "event interval then includes the other stream's kernels (LABNOTES.md 6)",
                        "note": "two independent prompt groups on two HIP streams, one host thread each; same kernels, same results"}
         res = {
-            "metric": "sampled+scored images/sec (whole node), SD3.5-large 1024^2 10-step G=4 (secondary line, BASELINE config 4 shapes)"
-            if c4 else ("sampled+scored images/sec (whole node), Qwen-Image MMDiT 1024^2 10-step G=8, DINO reward, fp8 Linears (secondary line, "
-                        "BASELINE config 5 shapes)" if c5 else ("sampled+scored images/sec (whole node), SD3-med 512^2 10-step G=8, DINOv2-patch "
-                        "adversarial reward (BASELINE config 3, rank-local work)" if c3 else "sampled+scored images/sec (whole node), SD3-med 512^2 10-step G=8 GRPO")),
-            "value": round(images / dt, 3), "unit": "images/s", "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "fp8" if c5 else "bf16", "data": "synthetic",
-            "config": {"workload": ("BASELINE config 5 shapes: Qwen-Image MMDiT (60 blocks, 24 heads x 128, D=3072; block Linears on fp8 e4m3 operands, "
-                                    "per-token x per-channel scales, f32 accumulation; attention / norms / embedders bf16) 1024x1024 = 4096 packed "
-                                    f"latent positions + {C5_TEXT_TOKENS} text tokens (3584-wide states of the Qwen2.5-VL text tower on synthetic token ids), 10 steps, CFG 4.5 as u + s (t - u) "
-                                    "(the rollout function's combine, PF:640-642, not QwenImagePipeline's norm-rescaled one), G=8, SDE window 2 @ noise 0.8 on "
-                                    "the SD3 sigma table (shift 3), VAE decode (" + pipe.vae.mode + ") with Qwen-Image's own decoder (AutoencoderKLQwenImage on one "
-                                    "frame: widths 384 / 192 / 96, per-pixel RMS norm), DINOv2-B/14 patch reward + head (RW:375-434), reward all-gather + group advantage")
-                                   if c5 else (("BASELINE config 4 shapes: SD3.5-large (38 blocks, D=2432) LoRA-merged 1024x1024, 10 steps, CFG 4.5, "
-                                    "G=4, SDE window 2 @ noise 0.8, VAE decode (fp32-equivalent; 3x3 convolutions: " + vae_ran + "), fp32-equivalent PickScore reward (ocr: stand-in "
-                                    "recogniser -- no PaddleOCR in this image, the OCR half of the reward is a constant and its host-side recognition costs nothing here), "
-                                    "reward all-gather + group advantage") if c4 else
-                                   ("BASELINE config " + ("3" if c3 else "2") + ": SD3.5-medium LoRA-merged 512x512, 10 steps, CFG 4.5, G=8, "
-                                    "SDE window 2 @ noise 0.8, VAE decode (fp32-equivalent; 3x3 convolutions: " + vae_ran + "), " +
-                                    ("co-trained DINOv2 ViT-B/14 @ 518 patch discriminator + head as reward (RW:375-434)" if c3 else
-                                     "PickScore (CLIP ViT-H/14) reward") + ", reward all-gather + group advantage")), "global_batch": world * G,
-                       "transformer_batch_per_gpu": 2 * G, "parallelism": f"dp{world} (prompt groups sharded)",
-                       "schedule": ("trainer default (config sample.groups_in_flight = 2, adv_grpo_amd/trainer.py sample_epoch): two prompt groups per rank rolled "
-                                    "out at the same time, one HIP stream + one host thread each (a group's VAE decode on that one stream), scores as reward futures on one scoring stream, "
-                                    "reward gather + group advantage per group on the main thread in group order; samples bit-identical to the serial "
-                                    "schedule (tests/test_gpu_trainer.py::test_groups_in_flight_do_not_change_the_samples)")
-                       if in_flight > 1 else "serial: one prompt group at a time on the launch stream, scores as reward futures"},
-            "effective_tflops_per_gpu": round(per_image_tflop * images / dt / world, 1),
-            "frac_of_bf16_mfma_peak": round(per_image_tflop * images / dt / world / BF16_DENSE_PEAK_TFLOPS, 4),
-            **({"frac_of_mixed_mfma_peak": round(mixed_peak_s * images / dt / world, 4),
-                "mixed_peak_is": "Linear FLOPs priced at the dense fp8 peak (5 PFLOP/s), attention / VAE / DINO FLOPs at the dense bf16 peak (2.5 PFLOP/s): "
-                                 "time at those peaks / measured time"} if c5 else {}),
+            **headline,
             "roofline": roofline,
             "serial": None if serial_dt is None else {
                 "ms_per_step": round(serial_dt / args.steps * 1e3, 2), "value": round(images / serial_dt, 3), "steps": args.steps,

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$R
 timeout 900 python -m pytest $R/tests/test_gpu_vit.py $R/tests/test_gpu_trainer.py $R/tests/test_gpu_rollout.py $R/tests/test_hub.py -m gpu -x -q > $O/tests_targeted.txt 2>&1
 tail -3 $O/tests_targeted.txt
-timeout 900 python $R/bench.py --steps 20 --warmup 5 > $O/bench_c2_driver_style.json 2> $O/bench_c2_driver_style.err
+timeout 900 python $R/bench.py --full --steps 20 --warmup 5 > $O/bench_c2_driver_style.json 2> $O/bench_c2_driver_style.err
 tail -c 600 $O/bench_c2_driver_style.err
 timeout 300 python $R/scripts/yardstick_matmul.py 2>/dev/null | grep -v amdgpu > $O/yardstick_matmul.txt
 timeout 300 python $R/scripts/yardstick_attention.py 2>/dev/null | grep -v amdgpu > $O/yardstick_attention.txt
@@ -20,7 +20,7 @@ for m in plain gelu gateres rms; do
   timeout 120 python $R/scripts/p8_stamps.py 16384 $N 1536 $m 2>/dev/null | grep -v amdgpu >> $O/p8_stamps.txt
 done
 unset ADVGRPO_LIB
-rocprofv3 --kernel-trace --stats -d $O/kt_c2 -o x -- python $R/bench.py --steps 3 --warmup 1 --no-epoch --no-cpu-baseline --no-pricing --schedule serial > $O/bench_c2_prof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $O/kt_c2 -o x -- python $R/bench.py --full --steps 3 --warmup 1 --no-epoch --no-cpu-baseline --no-pricing --schedule serial > $O/bench_c2_prof.json 2>/dev/null
 python $R/scripts/rocpd_stats.py $O/kt_c2/x_results.db $O/kernel_stats_c2.md > /dev/null
 python $R/scripts/gpu_idle.py $O/kt_c2/x_results.db > $O/gpu_idle_c2.txt
 rm -rf $O/kt_c2

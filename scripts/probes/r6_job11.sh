@@ -7,8 +7,8 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$R
 F="--steps 12 --warmup 3 --no-epoch --no-pricing --no-cpu-baseline"
-for i in 1 2 3; do timeout 600 python $R/bench.py $F > $O/bench_$i.json 2>/dev/null; done
-timeout 600 python $R/bench.py --steps 12 --warmup 3 --no-pricing --no-cpu-baseline > $O/bench_with_epoch.json 2>$O/bench_with_epoch.err
+for i in 1 2 3; do timeout 600 python $R/bench.py --full $F > $O/bench_$i.json 2>/dev/null; done
+timeout 600 python $R/bench.py --full --steps 12 --warmup 3 --no-pricing --no-cpu-baseline > $O/bench_with_epoch.json 2>$O/bench_with_epoch.err
 python - <<PY
 import json,glob
 for f in sorted(glob.glob("$O/*.json")):

@@ -7,10 +7,10 @@ cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$R
 F="--steps 12 --warmup 3 --no-epoch --no-pricing --no-cpu-baseline"
 for i in 1 2; do
-  timeout 600 python $R/bench.py $F > $O/base_$i.json 2>/dev/null
-  timeout 600 python $R/bench.py $F --decode-in-future 1 > $O/decode_in_future_$i.json 2>/dev/null
-  GPU_MAX_HW_QUEUES=4 timeout 600 python $R/bench.py $F > $O/hwq4_$i.json 2>/dev/null
-  GPU_MAX_HW_QUEUES=16 timeout 600 python $R/bench.py $F > $O/hwq16_$i.json 2>/dev/null
+  timeout 600 python $R/bench.py --full $F > $O/base_$i.json 2>/dev/null
+  timeout 600 python $R/bench.py --full $F --decode-in-future 1 > $O/decode_in_future_$i.json 2>/dev/null
+  GPU_MAX_HW_QUEUES=4 timeout 600 python $R/bench.py --full $F > $O/hwq4_$i.json 2>/dev/null
+  GPU_MAX_HW_QUEUES=16 timeout 600 python $R/bench.py --full $F > $O/hwq16_$i.json 2>/dev/null
 done
 python - <<PY
 import json,glob

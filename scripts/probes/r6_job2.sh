@@ -25,7 +25,7 @@ for i in 1 2; do
 done
 unset ADVGRPO_LIB
 export ADVGRPO_LIB=$R/adv_grpo_amd/libadvgrpo_base.so
-timeout 600 python $R/bench.py --steps 10 --warmup 3 --no-epoch --no-pricing --no-cpu-baseline > $O/bench_trainer_schedule.json 2>/dev/null
-timeout 600 python $R/bench.py --steps 10 --warmup 3 --no-epoch --no-pricing --no-cpu-baseline --cfg-streams > $O/bench_trainer_schedule_cfg_streams.json 2>/dev/null
+timeout 600 python $R/bench.py --full --steps 10 --warmup 3 --no-epoch --no-pricing --no-cpu-baseline > $O/bench_trainer_schedule.json 2>/dev/null
+timeout 600 python $R/bench.py --full --steps 10 --warmup 3 --no-epoch --no-pricing --no-cpu-baseline --cfg-streams > $O/bench_trainer_schedule_cfg_streams.json 2>/dev/null
 unset ADVGRPO_LIB
 ls -la $O

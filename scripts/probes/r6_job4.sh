@@ -17,6 +17,6 @@ sys.argv = ["bench_gstep.py"]
 runpy.run_path(sys.argv and __import__("os").environ["PYTHONPATH"] + "/scripts/bench_gstep.py", run_name="__main__")
 PY
 cat $O/gstep.txt $O/gstep_python_sequencing.txt
-timeout 900 python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err
+timeout 900 python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err
 tail -c 400 $O/bench_c2.err
 ls -la $O

@@ -30,6 +30,6 @@ for name, kw, c in (("f16x2 (default), C entry", {}, True), ("f16x2 (default), P
     print(f"{name}: {min(ts):.2f} ms per 8 x 512^2 decode (min of 3 x 5)   [{' '.join(f'{t:.2f}' for t in ts)}]")
 PY
 cat $O/vae_modes.txt
-timeout 900 python $R/bench.py --config c4 --steps 3 --warmup 1 > $O/bench_c4.json 2> $O/bench_c4.err
+timeout 900 python $R/bench.py --full --config c4 --steps 3 --warmup 1 > $O/bench_c4.json 2> $O/bench_c4.err
 tail -c 300 $O/bench_c4.err
 ls -la $O

@@ -8,10 +8,10 @@ cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$R
 timeout 900 python -m pytest $R/tests/test_gpu_vae.py -m gpu -x -q -k "c_entry or f16x1 or two_streams or 1024" > $O/tests.txt 2>&1
 tail -3 $O/tests.txt
-timeout 900 python $R/bench.py --config c4 --steps 2 --warmup 1 --no-pricing > $O/bench_c4.json 2> $O/bench_c4.err
+timeout 900 python $R/bench.py --full --config c4 --steps 2 --warmup 1 --no-pricing > $O/bench_c4.json 2> $O/bench_c4.err
 tail -c 300 $O/bench_c4.err
 for i in 1 2; do
-  timeout 600 python $R/bench.py --steps 10 --warmup 3 --no-epoch --no-pricing --no-cpu-baseline > $O/bench_c2_two_stream_decode_$i.json 2>/dev/null
-  timeout 600 python $R/bench.py --steps 10 --warmup 3 --no-epoch --no-pricing --no-cpu-baseline --vae-one-stream > $O/bench_c2_one_stream_decode_$i.json 2>/dev/null
+  timeout 600 python $R/bench.py --full --steps 10 --warmup 3 --no-epoch --no-pricing --no-cpu-baseline > $O/bench_c2_two_stream_decode_$i.json 2>/dev/null
+  timeout 600 python $R/bench.py --full --steps 10 --warmup 3 --no-epoch --no-pricing --no-cpu-baseline --vae-one-stream > $O/bench_c2_one_stream_decode_$i.json 2>/dev/null
 done
 ls -la $O

@@ -8,9 +8,9 @@ cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$R
 F="--steps 12 --warmup 3 --no-epoch --no-pricing --no-cpu-baseline"
 for i in 1 2; do
-  timeout 600 python $R/bench.py $F > $O/g2_$i.json 2>/dev/null
-  timeout 600 python $R/bench.py $F --groups-in-flight 3 > $O/g3_$i.json 2>/dev/null
-  timeout 600 python $R/bench.py $F --sync-scoring > $O/g2_sync_scoring_$i.json 2>/dev/null
+  timeout 600 python $R/bench.py --full $F > $O/g2_$i.json 2>/dev/null
+  timeout 600 python $R/bench.py --full $F --groups-in-flight 3 > $O/g3_$i.json 2>/dev/null
+  timeout 600 python $R/bench.py --full $F --sync-scoring > $O/g2_sync_scoring_$i.json 2>/dev/null
 done
 timeout 900 python -m pytest $R/tests/test_gpu_trainer.py -m gpu -x -q > $O/tests_trainer.txt 2>&1
 tail -3 $O/tests_trainer.txt

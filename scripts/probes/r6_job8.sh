@@ -6,7 +6,7 @@ O=$R/gpurun_out/r6_job8
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$R
-for i in 1 2; do timeout 600 python $R/bench.py --steps 12 --warmup 3 --no-epoch --no-pricing --no-cpu-baseline > $O/bench_$i.json 2>$O/bench_$i.err; done
+for i in 1 2; do timeout 600 python $R/bench.py --full --steps 12 --warmup 3 --no-epoch --no-pricing --no-cpu-baseline > $O/bench_$i.json 2>$O/bench_$i.err; done
 python - <<PY
 import json,glob
 for f in sorted(glob.glob("$O/bench_*.json")):

@@ -9,13 +9,13 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 FAST="--steps 3 --warmup 1 --no-epoch --no-cpu-baseline --no-pricing --schedule serial"     # (kernel tables: the serial schedule only)
 # 1. driver-style lines
-python $R/bench.py --steps 5 --warmup 2 > $O/bench_c2.json 2> $O/bench_c2.err
-python $R/bench.py --config c4 --steps 3 --warmup 1 > $O/bench_c4.json 2> $O/bench_c4.err
-python $R/bench.py --config c3 --steps 5 --warmup 2 > $O/bench_c3.json 2> $O/bench_c3.err
-python $R/bench.py --config c5 --steps 3 --warmup 1 > $O/bench_c5.json 2> $O/bench_c5.err
-rocprofv3 --kernel-trace --stats -d $O/kt_c5 -o x -- python $R/bench.py --config c5 --steps 1 --warmup 1 --no-pricing --no-epoch > $O/bench_c5_prof.json 2>/dev/null
+python $R/bench.py --full --steps 5 --warmup 2 > $O/bench_c2.json 2> $O/bench_c2.err
+python $R/bench.py --full --config c4 --steps 3 --warmup 1 > $O/bench_c4.json 2> $O/bench_c4.err
+python $R/bench.py --full --config c3 --steps 5 --warmup 2 > $O/bench_c3.json 2> $O/bench_c3.err
+python $R/bench.py --full --config c5 --steps 3 --warmup 1 > $O/bench_c5.json 2> $O/bench_c5.err
+rocprofv3 --kernel-trace --stats -d $O/kt_c5 -o x -- python $R/bench.py --full --config c5 --steps 1 --warmup 1 --no-pricing --no-epoch > $O/bench_c5_prof.json 2>/dev/null
 python $R/scripts/rocpd_stats.py $O/kt_c5/x_results.db $O/kernel_stats_c5.md > /dev/null
-rocprofv3 --kernel-trace --stats -d $O/kt_c3 -o x -- python $R/bench.py --config c3 --steps 1 --warmup 1 --no-pricing > $O/bench_c3_prof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $O/kt_c3 -o x -- python $R/bench.py --full --config c3 --steps 1 --warmup 1 --no-pricing > $O/bench_c3_prof.json 2>/dev/null
 python $R/scripts/rocpd_stats.py $O/kt_c3/x_results.db $O/kernel_stats_c3_with_epoch_legs.md > /dev/null
 python $R/scripts/bench_attention_d128.py 10 > $O/attention_d128.txt 2>/dev/null
 python $R/scripts/bench_attention.py 2>/dev/null | grep -v amdgpu > $O/attention_fwd_d64.txt
@@ -32,7 +32,7 @@ python $R/scripts/rocpd_stats.py $O/kt_gq/x_results.db $O/kernel_stats_gstep_qwe
 GRAFT_REPO_ROOT=$R bash $R/scripts/probes/pmc_attention_bwd.sh 2 >> $O/attention_bwd.txt 2>/dev/null
 cd /tmp
 # 2. kernel tables: rollout (timed configuration only) and one G-step micro-batch
-rocprofv3 --kernel-trace --stats -d $O/kt_c2 -o x -- python $R/bench.py $FAST > $O/bench_c2_prof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats -d $O/kt_c2 -o x -- python $R/bench.py --full $FAST > $O/bench_c2_prof.json 2>/dev/null
 python $R/scripts/rocpd_stats.py $O/kt_c2/x_results.db $O/kernel_stats_c2.md > /dev/null
 python $R/scripts/gpu_idle.py $O/kt_c2/x_results.db > $O/gpu_idle_c2.txt
 python $R/scripts/bench_gstep.py 2>/dev/null | grep -v amdgpu > $O/gstep.txt              # the number: without the profiler attached
@@ -51,13 +51,13 @@ python $R/scripts/rocpd_stats.py $O/kt_gstep_s/x_results.db $O/kernel_stats_gste
 # 3. HBM-side traffic (separate passes, MI355X_MICROARCH "HBM"), per config
 for cfg in c2 c4 c5; do
   for c in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --pmc $c --output-format csv -d $O/pmc_${cfg}_$c -o x -- python $R/bench.py --config $cfg --steps 1 --warmup 1 --no-epoch --no-cpu-baseline --no-pricing --schedule serial > /dev/null 2>&1
+    rocprofv3 --pmc $c --output-format csv -d $O/pmc_${cfg}_$c -o x -- python $R/bench.py --full --config $cfg --steps 1 --warmup 1 --no-epoch --no-cpu-baseline --no-pricing --schedule serial > /dev/null 2>&1
   done
   mkdir -p $O/pmc_$cfg && cp -r $O/pmc_${cfg}_FETCH_SIZE $O/pmc_${cfg}_WRITE_SIZE $O/pmc_$cfg/
   python $R/scripts/pmc_traffic.py $O/pmc_$cfg $O/pmc_traffic_$cfg.json > $O/pmc_traffic_$cfg.txt
 done
 # 4. matrix-pipe busy share of the MFMA kernels
-rocprofv3 --pmc SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY -d $O/pmc_mfma -o x -- python $R/bench.py --steps 1 --warmup 1 --no-epoch --no-cpu-baseline --no-pricing --schedule serial > /dev/null 2>&1
+rocprofv3 --pmc SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY -d $O/pmc_mfma -o x -- python $R/bench.py --full --steps 1 --warmup 1 --no-epoch --no-cpu-baseline --no-pricing --schedule serial > /dev/null 2>&1
 python $R/scripts/pmc_db.py $O/pmc_mfma/x_results.db advgrpo > $O/pmc_mfma.txt
 rm -rf $O/kt_c2 $O/kt_c3 $O/kt_c5 $O/kt_gstep $O/kt_gstep_s $O/kt_gq $O/pmc_c2* $O/pmc_c4_* $O/pmc_c4 $O/pmc_c5_* $O/pmc_c5 $O/pmc_mfma
 ls -la $O

@@ -44,3 +44,35 @@ def test_gpus_gt_1_without_launcher_takes_the_spawn_path(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert "GPU(s) visible" in str(e.value)
+
+
+def test_dump_outputs_keeps_to_the_limit_and_samples_the_same_elements(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files, whole when they fit, else a seeded sample that depends on name and shape only."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20_000)
+    g = torch.Generator().manual_seed(0)
+    arrays = {"images": torch.rand(4, 3, 32, 32, generator=g), "log_probs": torch.randn(4, 2, generator=g).to(torch.bfloat16),
+              "timesteps": torch.arange(8, dtype=torch.int32).reshape(4, 2).float()}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["images.npy", "log_probs.npy", "timesteps.npy"]
+    total = sum((tmp_path / "a" / f).stat().st_size for f in files)
+    assert total <= 20_000 + 3 * 256
+    lp = np.load(tmp_path / "a" / "log_probs.npy")
+    assert lp.dtype == np.float32 and np.array_equal(lp, arrays["log_probs"].float().numpy())
+    im_a, im_b = np.load(tmp_path / "a" / "images.npy"), np.load(tmp_path / "b" / "images.npy")
+    assert im_a.dtype == np.float32 and im_a.ndim == 1 and 0 < im_a.size < 4 * 3 * 32 * 32
+    assert np.array_equal(im_a, im_b) and np.isin(im_a, arrays["images"].numpy().reshape(-1)).all()
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (4, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"

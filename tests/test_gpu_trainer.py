@@ -397,7 +397,7 @@ def test_bench_self_spawn_path_at_world_1():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--spawn", "--steps", "1", "--warmup", "1",
-                        "--no-epoch", "--no-cpu-baseline", "--no-pricing"], capture_output=True, text=True, timeout=900)
+                        "--full", "--no-epoch", "--no-cpu-baseline", "--no-pricing"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["ranks_seen"] == 1 and line["value"] > 0
@@ -406,6 +406,28 @@ def test_bench_self_spawn_path_at_world_1():
     assert len(sd["ms_per_step_by_rank"]["all"]) == 1 and sd["ms_per_step_by_rank"]["max"] > 0
     assert sd["reward_all_gather_ms"] >= 0 and sd["lora_gradient_all_reduce_ms"] >= 0 and sd["lora_gradient_bytes"] == 18_776_064 * 4
     assert sd["value_at_n1_same_run"] > 0 and 0.8 < sd["value_over_n_times_n1"] < 1.25
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` line carries the headline and none of the --full legs; --dump-outputs writes the last timed step's arrays."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["unit"] == "images/s" and line["higher_is_better"] is True and line["dtype"] == "bf16" and line["steps"] == 2
+    assert line["value"] > 0 and abs(line["value"] - 2 * 8 / (line["ms_per_step"] * 2e-3)) < 0.01 * line["value"]
+    assert not {"roofline", "serial", "epoch", "vae", "cpu_baseline", "clock_and_power", "scaling_diagnostics"} & set(line)
+    arrays = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert set(arrays) == {"images", "latents", "log_probs", "timesteps", "rewards", "advantages"}
+    assert sum(p.stat().st_size for p in out.glob("*.npy")) <= 64_000_000
+    assert arrays["images"].shape == (8, 3, 512, 512) and arrays["log_probs"].shape == (8, 2) and arrays["rewards"].shape == (8,)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
 
 
 @pytest.mark.parametrize("model,preset,extra", [
@@ -441,7 +463,7 @@ def test_bench_world_2_end_to_end_on_one_gpu():
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29577", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--no-pricing"], capture_output=True, text=True, timeout=900, env=env)
+                        "--full", "--no-pricing"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and line["value"] > 0 and line["scaling"] == "weak"

@@ -1,8 +1,7 @@
 """Pins oracle/text_encoders.py: against transformers' CLIPTextModelWithProjection / T5EncoderModel built
-from small random configs, and against the REFERENCE's own encode_prompt run on those modules (imported from
-/root/reference when it is present -- it never is on the GPU box, where only the transformers pin runs)."""
+from small random configs, and against the REFERENCE's own encode_prompt run on those modules (its outputs stored in
+tests/golden/encode_prompt.npz)."""
 import os
-import sys
 
 import pytest
 import torch
@@ -52,19 +51,16 @@ def test_oracle_matches_transformers_modules():
         assert torch.allclose(got, ref, atol=2e-5, rtol=1e-4)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/adv_grpo"), reason="reference tree not present (GPU box)")
 def test_oracle_matches_reference_encode_prompt():
-    sys.path.insert(0, "/root/reference")
-    try:
-        from adv_grpo.diffusers_patch.train_dreambooth_lora_sd3 import encode_prompt as ref_encode
-    finally:
-        sys.path.pop(0)
+    """tests/golden/encode_prompt.npz = the reference's encode_prompt on these same seeded modules (make_golden_encode_prompt.py)."""
+    import numpy as np
     from oracle import text_encoders as te
     cl, cg, t5, ids, ids_t5 = _models(3)
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "encode_prompt.npz"))
+    assert np.array_equal(ids.numpy(), g["ids"]) and np.array_equal(ids_t5.numpy(), g["ids_t5"])
+    pe_ref, pooled_ref = torch.from_numpy(g["prompt_embeds"]), torch.from_numpy(g["pooled"])
     L, G, T = _specs(cl, cg, t5)
     with torch.no_grad():
-        pe_ref, pooled_ref = ref_encode([cl, cg, t5], [None, None, None], ["a", "b"], 40, device="cpu",
-                                        text_input_ids_list=[ids, ids, ids_t5])
         pe, pooled = te.encode_prompt(L, G, T, ids, ids, ids_t5)
     assert pe.shape == pe_ref.shape == (2, 77 + 40, 256) and pooled.shape == pooled_ref.shape == (2, 48 + 80)
     assert torch.allclose(pe, pe_ref, atol=2e-5, rtol=1e-4) and torch.allclose(pooled, pooled_ref, atol=2e-5, rtol=1e-4)
