@@ -4,8 +4,8 @@ Mirror of adv_grpo/rewards.py:1012-1095: ``multi_score(device, {name: weight}) -
 metadata, scorer=None, ref_images=None, only_strict=True, head=None, ...) -> ({name: scores, ..., 'avg':
 [...]}, {})`` with the same name-dispatched calling conventions (factory takes ``device`` iff it has a
 parameter of that name; co-train scorers receive the backbone / head as arguments).  Registered: the six
-scorers on the hot path; the remote-server / VLM scorers are out of scope and raise a
-clear error.  New scorers can be added with ``register_scorer``.
+scorers on the hot path and ``jpeg_compressibility`` (on-device JPEG, jpeg.py); the remote-server /
+VLM scorers are out of scope and raise a clear error.  New scorers can be added with ``register_scorer``.
 """
 import inspect
 
@@ -13,7 +13,7 @@ import torch
 
 from . import vit
 
-_OUT_OF_SCOPE = ("deqa", "video_ocr", "imagereward", "qwenvl", "aesthetic", "jpeg_compressibility", "unifiedreward",
+_OUT_OF_SCOPE = ("deqa", "video_ocr", "imagereward", "qwenvl", "aesthetic", "unifiedreward",
                  "geneval", "clipscore", "image_similarity_eval", "constractive_external", "discriminator",
                  "pickscore_patch", "dino_multi_cotrain", "siglip_cotrain", "siglip_image_similarity")
 # scorers a shipped experiment of config/grpo.py names although they are outside SURVEY.md 8's six: why, per name
@@ -154,6 +154,29 @@ def ocr_score(device):
     return _fn
 
 
+def jpeg_incompressibility():
+    """rewards.py:13-25: quality-95 JPEG size / 1000 (float64), from the on-device encoder (jpeg.py, byte-exact with Pillow);
+    images: device [N,3,H,W] in [0,1] (f32 / bf16) or a uint8 NHWC array.  Stays on the device, no sync."""
+    from . import jpeg
+
+    def _fn(images, prompts, metadata):
+        s = jpeg.sizes(images, quality=95).to(torch.float64)
+        # divide by a device scalar: torch turns a division by a python number into a reciprocal multiply, and the
+        # reference's numpy division is correctly rounded
+        return s / torch.full((), 1000.0, dtype=torch.float64, device=s.device), {}
+    return _fn
+
+
+def jpeg_compressibility():
+    """rewards.py:28-35: -(size / 1000) / 500."""
+    jpeg_fn = jpeg_incompressibility()
+
+    def _fn(images, prompts, metadata):
+        rew, meta = jpeg_fn(images, prompts, metadata)
+        return -rew / torch.full((), 500.0, dtype=torch.float64, device=rew.device), meta
+    return _fn
+
+
 score_functions = {
     "ocr": ocr_score,
     "pickscore": pickscore_score,
@@ -161,6 +184,7 @@ score_functions = {
     "pickscore_cotrain": pickscore_cotrain_score,
     "dino_cotrain": dino_cotrain_score,
     "dino_patch_cotrain": dino_patch_cotrain_score,
+    "jpeg_compressibility": jpeg_compressibility,
 }
 
 

@@ -26,7 +26,7 @@ extern "C" {
 
 #define ADVGRPO_ABI_VERSION 1
 
-enum advgrpo_dtype { ADVGRPO_F32 = 0, ADVGRPO_BF16 = 1, ADVGRPO_F64 = 2 };
+enum advgrpo_dtype { ADVGRPO_F32 = 0, ADVGRPO_BF16 = 1, ADVGRPO_F64 = 2, ADVGRPO_U8 = 3 };
 
 int advgrpo_abi_version(void);
 const char* advgrpo_last_error(void);
@@ -696,6 +696,22 @@ int advgrpo_softmax_bwd_rows(const float* sc, const float* dp, void* p16, void* 
 int advgrpo_colsum_bf16(const void* x, int64_t ld, int R, int C, float* out /* += */, void* stream);
 int advgrpo_ln_affine_grads(const void* x, int64_t ldx, const void* dy, int64_t lddy, int M, int D, float eps,
                             float* grad_w /* += */, float* grad_b /* += */, void* stream);
+
+/* ------------------------------------------------------------------ JPEG (compressibility reward)
+ * Baseline sequential JPEG of every image, byte-exact with PIL.Image.save(format="JPEG", quality=quality) (Pillow /
+ * libjpeg-turbo defaults: 4:2:0, the Annex K Huffman tables, no restart markers, a 623-byte JFIF header).  Replaces the
+ * host round trip of jpeg_incompressibility / jpeg_compressibility (adv_grpo/rewards.py:13-35).
+ * images: [N,3,H,W] (layout NCHW) or [N,H,W,3] (NHWC); dtype F32 / BF16 (pixels in [0,1], quantised on the fly as
+ * (x*255).round().clamp(0,255) in that dtype) or U8.  H, W: positive multiples of 16 (<= 65535); quality 1..100.
+ * sizes: int64 [N], the file size in bytes.  files: NULL, or uint8 [N, file_stride] receiving the complete .jpg files
+ * (file_stride >= advgrpo_jpeg_max_file_bytes(H, W), a worst-case bound).
+ * workspace: >= advgrpo_jpeg_workspace_bytes(N, H, W) bytes, 256-byte aligned.  The size queries return -1 for a refused
+ * geometry. */
+enum advgrpo_jpeg_layout { ADVGRPO_JPEG_NCHW = 0, ADVGRPO_JPEG_NHWC = 1 };
+int64_t advgrpo_jpeg_workspace_bytes(int N, int H, int W);
+int64_t advgrpo_jpeg_max_file_bytes(int H, int W);
+int advgrpo_jpeg_encode(const void* images, int dtype, int layout, int N, int H, int W, int quality, int64_t* sizes,
+                        uint8_t* files, int64_t file_stride, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,8 @@
   python scripts/train_sd3_fast.py --config config/grpo.py:dino_cotrain_sd3_patch_fast --model Qwen/Qwen-Image --resolution 1024 \
          --linear-dtype fp8 --images-per-prompt 8 --batches 1          (BASELINE config 5)
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 scripts/train_sd3_fast.py --config ...
+  python scripts/train_sd3_fast.py --config config/grpo.py:pickscore_sd3_fast --reward-fn jpeg_compressibility=1
+         (the GRPO sanity check: a reward that needs no scorer weights and has to rise over epochs)
 
   python scripts/train_sd3_fast.py --config ... --weights <local snapshot of config.pretrained.model> \
          --pickscore-weights <PickScore_v1 dir> | --dino-weights <timm vit_base_patch14_dinov2 dir>      (real checkpoints, adv_grpo_amd/hub.py)
@@ -22,9 +24,25 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")    # before the HIP runtime star
 import torch  # noqa: E402
 
 
+def parse_reward_fn(text):
+    """`NAME=W[,NAME=W]` -> {name: weight} (the shape of config.reward_fn, config/grpo.py)."""
+    out = {}
+    for item in text.split(","):
+        name, sep, w = item.partition("=")
+        if not sep or not name.strip():
+            raise argparse.ArgumentTypeError(f"--reward-fn: expected NAME=W[,NAME=W], got {text!r}")
+        try:
+            out[name.strip()] = float(w) if any(ch in w for ch in ".eE") else int(w)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"--reward-fn: weight of {name.strip()!r} is not a number: {w!r}") from None
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True)
+    ap.add_argument("--reward-fn", type=parse_reward_fn, default=None, metavar="NAME=W[,NAME=W]",
+                    help="override config.reward_fn, e.g. jpeg_compressibility=1 (the one reward that needs no scorer weights)")
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--layers", type=int, default=None, help="reduce the MMDiT depth (smoke runs)")
     ap.add_argument("--batches", type=int, default=None, help="override sample.num_batches_per_epoch")
@@ -59,10 +77,14 @@ def main():
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     from adv_grpo_amd.config.experiments import parse_config_flag
     cfg = parse_config_flag(args.config, gpu_number=world)
+    if args.reward_fn is not None:
+        cfg.reward_fn = args.reward_fn
     from adv_grpo_amd import rewards as _rw                      # (before any device is touched: a refused experiment costs nothing)
     for rname in list(cfg.reward_fn.keys()):
         if rname in _rw._OUT_OF_SCOPE:
             raise SystemExit(f"{args.config}: reward '{rname}': " + _rw._WHY_NOT.get(rname, "outside the accelerated hot path (SURVEY.md 2.1 row 5)"))
+        if rname not in _rw.score_functions:
+            raise SystemExit(f"{args.config}: unknown reward '{rname}' (registered: {', '.join(sorted(_rw.score_functions))})")
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
     if world > 1:
