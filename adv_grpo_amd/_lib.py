@@ -145,6 +145,7 @@ SIGNATURES = {
     "advgrpo_attention_fwd_bias": (c_int, [_P, _P, _P, _P] + [c_int64] * 8 + [c_int] * 5 + [c_float, c_int, _P, _P]),
     "advgrpo_gemm_bf16_train": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int, c_int, c_int, c_int, _P, c_int,
                                         c_float, _P, c_int64, c_int, _P, c_int64, _P, _P, c_int64, c_int, _P]),
+    "advgrpo_gemm_bf16_acc_f32": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int, c_int, c_int, c_float, _P]),
     "advgrpo_gemm_tn_f32acc": (c_int, [_P, c_int64, c_int, c_int64, c_int64, _P, c_int64, c_int, c_int64, c_int64, _P, c_int64,
                                        c_int, c_int, c_int, c_int, c_float, _P, _P]),
     "advgrpo_gemm_tn_workspace_bytes": (c_int64, [c_int, c_int]),
@@ -181,7 +182,8 @@ SIGNATURES = {
     "advgrpo_clip_pair_loss_labels": (c_int, [_P, _P, c_int, c_int, c_float, _P, _P, _P, _P, _P]),
     "advgrpo_softmax_bwd_rows": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_float, _P]),
     "advgrpo_colsum_bf16": (c_int, [_P, c_int64, c_int, c_int, _P, _P]),
-    "advgrpo_ln_affine_grads": (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, c_float, _P, _P, _P]),
+    "advgrpo_ln_affine_grads_workspace_bytes": (c_int64, [c_int]),
+    "advgrpo_ln_affine_grads": (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, c_float, _P, _P, _P, _P]),
     "advgrpo_dino_head_dpre": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     "advgrpo_timestep_embedding": (c_int, [_P, _P, c_int, c_int, _P]),
     "advgrpo_unary": (c_int, [_P, _P, _P, c_int64, c_int, _P]),

@@ -7,7 +7,8 @@
 //     backward fills dq (CLS row only), dk, dv (all rows) of a packed dqkv buffer.  No flash machinery needed.
 //   * clip_pair_loss: L2-normalise, 2-way CE on the diagonal text->image logits (= mean softplus(s(t.f1 - t.f0))),
 //     gradient w.r.t. the un-normalised image embeddings in the same launch.
-//   * column sums (bias gradients) and LayerNorm affine gradients as atomic f32 reductions.
+//   * column sums (bias gradients) and LayerNorm affine gradients as column-strip reductions in a fixed order (no float
+//     atomics anywhere: Adam turns last-bit noise of a near-zero gradient into a step of +-lr, so every sum here is repeatable).
 // Everything else of the D-step (Linears, weight gradients, LayerNorm dx, Adam) reuses the GEMM / row kernels.
 #include "common.hpp"
 
@@ -101,61 +102,87 @@ __global__ __launch_bounds__(64) void cls_attention_bwd_kernel(const bf16_t* __r
 }
 
 // e: [2B, P] image embeddings (real rows first), t: [B, P] text embeddings, both un-normalised bf16.
-// loss = mean_i softplus(s * (t^_i . e^1_i - t^_i . e^0_i)); de = d loss / d e (bf16).  One wave per pair.
+// loss = mean_i softplus(s * (t^_i . e^1_i - t^_i . e^0_i)); de = d loss / d e (bf16).  One workgroup of CLIP_LOSS_WAVES waves:
+// wave w takes pairs w, w + CLIP_LOSS_WAVES, ... and the wave partials of the loss are added in wave order (fixed order, no atomics).
 // With per-pair labels (CLIPCriterion.calc_loss, pick_score_training.py:172-186, in_batch_negatives = False): z = s (cos1 - cos0),
 // loss_i = label_0 softplus(z) + label_1 softplus(-z) + [label_0 == label_1] log(0.5); lab0 == nullptr means (1, 0), the only pair
 // the reference's caller passes (TP:170-171).
-__global__ __launch_bounds__(64) void clip_pair_loss_kernel(const bf16_t* __restrict__ e, const bf16_t* __restrict__ t, int B,
-                                                            int P, float s, const float* __restrict__ lab0,
-                                                            const float* __restrict__ lab1, float* __restrict__ loss,
-                                                            bf16_t* __restrict__ de) {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    const bf16_t* e0 = e + (int64_t)i * P;
-    const bf16_t* e1 = e + (int64_t)(B + i) * P;
-    const bf16_t* ti = t + (int64_t)i * P;
-    float n0 = 0.f, n1 = 0.f, nt = 0.f, d0 = 0.f, d1 = 0.f;
-    for (int k = lane; k < P; k += 64) {
-        const float a = bf2f(e0[k]), c = bf2f(e1[k]), u = bf2f(ti[k]);
-        n0 += a * a; n1 += c * c; nt += u * u; d0 += a * u; d1 += c * u;
+constexpr int CLIP_LOSS_WAVES = 16;
+__global__ __launch_bounds__(64 * CLIP_LOSS_WAVES) void clip_pair_loss_kernel(const bf16_t* __restrict__ e, const bf16_t* __restrict__ t,
+                                                                              int B, int P, float s, const float* __restrict__ lab0,
+                                                                              const float* __restrict__ lab1, float* __restrict__ loss,
+                                                                              bf16_t* __restrict__ de) {
+    __shared__ float part[CLIP_LOSS_WAVES];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float lsum = 0.f;
+    for (int i = wv; i < B; i += CLIP_LOSS_WAVES) {
+        const bf16_t* e0 = e + (int64_t)i * P;
+        const bf16_t* e1 = e + (int64_t)(B + i) * P;
+        const bf16_t* ti = t + (int64_t)i * P;
+        float n0 = 0.f, n1 = 0.f, nt = 0.f, d0 = 0.f, d1 = 0.f;
+        for (int k = lane; k < P; k += 64) {
+            const float a = bf2f(e0[k]), c = bf2f(e1[k]), u = bf2f(ti[k]);
+            n0 += a * a; n1 += c * c; nt += u * u; d0 += a * u; d1 += c * u;
+        }
+        n0 = sqrtf(wave_sum(n0)); n1 = sqrtf(wave_sum(n1)); nt = sqrtf(wave_sum(nt));
+        d0 = wave_sum(d0) / (n0 * nt);   // cos(t, e0)
+        d1 = wave_sum(d1) / (n1 * nt);
+        const float z = s * (d1 - d0);
+        const float sp = z > 20.f ? z : log1pf(__expf(z));
+        const float sig = 1.0f / (1.0f + __expf(-z));
+        float li = sp, gz = sig;
+        if (lab0) {
+            const float l0 = lab0[i], l1 = lab1[i];
+            const float spn = -z > 20.f ? -z : log1pf(__expf(-z));          // softplus(-z): cross entropy against image 1
+            li = l0 * sp + l1 * spn + (l0 == l1 ? -0.6931471805599453f : 0.f);
+            gz = l0 * sig - l1 * (1.0f - sig);
+        }
+        lsum += li / (float)B;
+        const float g = gz * s / (float)B;               // d loss / d cos1 ; d loss / d cos0 = -g
+        for (int k = lane; k < P; k += 64) {
+            const float a = bf2f(e0[k]) / n0, c = bf2f(e1[k]) / n1, u = bf2f(ti[k]) / nt;
+            // d cos / d e = (t^ - e^ cos) / |e|
+            de[(int64_t)i * P + k] = f2bf(-g * (u - a * d0) / n0);
+            de[(int64_t)(B + i) * P + k] = f2bf(g * (u - c * d1) / n1);
+        }
     }
-    n0 = sqrtf(wave_sum(n0)); n1 = sqrtf(wave_sum(n1)); nt = sqrtf(wave_sum(nt));
-    d0 = wave_sum(d0) / (n0 * nt);   // cos(t, e0)
-    d1 = wave_sum(d1) / (n1 * nt);
-    const float z = s * (d1 - d0);
-    const float sp = z > 20.f ? z : log1pf(__expf(z));
-    const float sig = 1.0f / (1.0f + __expf(-z));
-    float li = sp, gz = sig;
-    if (lab0) {
-        const float l0 = lab0[i], l1 = lab1[i];
-        const float spn = -z > 20.f ? -z : log1pf(__expf(-z));          // softplus(-z): cross entropy against image 1
-        li = l0 * sp + l1 * spn + (l0 == l1 ? -0.6931471805599453f : 0.f);
-        gz = l0 * sig - l1 * (1.0f - sig);
-    }
-    if (lane == 0) atomicAdd(loss, li / (float)B);
-    const float g = gz * s / (float)B;               // d loss / d cos1 ; d loss / d cos0 = -g
-    for (int k = lane; k < P; k += 64) {
-        const float a = bf2f(e0[k]) / n0, c = bf2f(e1[k]) / n1, u = bf2f(ti[k]) / nt;
-        // d cos / d e = (t^ - e^ cos) / |e|
-        de[(int64_t)i * P + k] = f2bf(-g * (u - a * d0) / n0);
-        de[(int64_t)(B + i) * P + k] = f2bf(g * (u - c * d1) / n1);
+    if (lane == 0) part[wv] = lsum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float tot = 0.f;
+        for (int w = 0; w < CLIP_LOSS_WAVES; ++w) tot += part[w];
+        loss[0] = tot;
     }
 }
+
+// Column reductions in a fixed order.  A workgroup of STRIP_WAVES waves owns 64 adjacent columns, one per lane; wave w walks
+// rows w, w + STRIP_WAVES, ... in increasing order, then wave 0 adds the STRIP_WAVES partials of its column in wave order.  Which
+// workgroup runs first does not matter: no two of them touch the same column.
+constexpr int STRIP_WAVES = 16;
 
 // out[c] += sum_r x[r, c]   (bias gradients)
-__global__ __launch_bounds__(256) void colsum_kernel(const bf16_t* __restrict__ x, int64_t ld, int R, int C,
-                                                     float* __restrict__ out) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    const int r0 = blockIdx.y * 64, r1 = min(R, r0 + 64);
+__global__ __launch_bounds__(64 * STRIP_WAVES) void colsum_kernel(const bf16_t* __restrict__ x, int64_t ld, int R, int C,
+                                                                  float* __restrict__ out) {
+    __shared__ float part[STRIP_WAVES][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
     float s = 0.f;
-    for (int r = r0; r < r1; ++r) s += bf2f(x[(int64_t)r * ld + c]);
-    atomicAdd(&out[c], s);
+    if (c < C) {
+#pragma unroll 8
+        for (int r = wv; r < R; r += STRIP_WAVES) s += bf2f(x[(int64_t)r * ld + c]);
+    }
+    part[wv][lane] = s;
+    __syncthreads();
+    if (wv == 0 && c < C) {
+        float t = 0.f;
+        for (int w = 0; w < STRIP_WAVES; ++w) t += part[w][lane];
+        out[c] += t;
+    }
 }
 
-// LayerNorm affine gradients: gw[c] += sum_r dy[r,c] * xhat[r,c];  gb[c] += sum_r dy[r,c].  One row per wave.
-__global__ __launch_bounds__(256) void ln_affine_grads_kernel(const bf16_t* __restrict__ x, int64_t ldx,
-                                                              const bf16_t* __restrict__ dy, int64_t lddy, int M, int D,
-                                                              float eps, float* __restrict__ gw, float* __restrict__ gb) {
+// LayerNorm affine gradients, pass 1: stats[2 r] = mean, stats[2 r + 1] = rstd of row r (two-pass variance).  One row per wave.
+__global__ __launch_bounds__(256) void ln_row_stats_kernel(const bf16_t* __restrict__ x, int64_t ldx, int M, int D, float eps,
+                                                           float* __restrict__ stats) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
@@ -165,10 +192,34 @@ __global__ __launch_bounds__(256) void ln_affine_grads_kernel(const bf16_t* __re
     float sq = 0.f;
     for (int d = lane; d < D; d += 64) { const float v = bf2f(x[(int64_t)row * ldx + d]) - mean; sq += v * v; }
     const float rstd = rsqrtf(wave_sum(sq) / (float)D + eps);
-    for (int d = lane; d < D; d += 64) {
-        const float g = bf2f(dy[(int64_t)row * lddy + d]);
-        atomicAdd(&gw[d], g * (bf2f(x[(int64_t)row * ldx + d]) - mean) * rstd);
-        atomicAdd(&gb[d], g);
+    if (lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
+}
+
+// pass 2: gw[c] += sum_r dy[r,c] * xhat[r,c];  gb[c] += sum_r dy[r,c]  (column strips, as colsum_kernel)
+__global__ __launch_bounds__(64 * STRIP_WAVES) void ln_affine_grads_kernel(const bf16_t* __restrict__ x, int64_t ldx,
+                                                                           const bf16_t* __restrict__ dy, int64_t lddy, int M, int D,
+                                                                           const float* __restrict__ stats, float* __restrict__ gw,
+                                                                           float* __restrict__ gb) {
+    __shared__ float part[2][STRIP_WAVES][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    float sw = 0.f, sb = 0.f;
+    if (c < D) {
+#pragma unroll 4
+        for (int r = wv; r < M; r += STRIP_WAVES) {
+            const float g = bf2f(dy[(int64_t)r * lddy + c]);
+            sw += g * (bf2f(x[(int64_t)r * ldx + c]) - stats[2 * r]) * stats[2 * r + 1];
+            sb += g;
+        }
+    }
+    part[0][wv][lane] = sw;
+    part[1][wv][lane] = sb;
+    __syncthreads();
+    if (wv == 0 && c < D) {
+        float tw = 0.f, tb = 0.f;
+        for (int w = 0; w < STRIP_WAVES; ++w) { tw += part[0][w][lane]; tb += part[1][w][lane]; }
+        gw[c] += tw;
+        gb[c] += tb;
     }
 }
 
@@ -200,8 +251,7 @@ extern "C" int advgrpo_clip_pair_loss(const void* image_embs, const void* text_e
                                       float* loss, void* d_image_embs, void* stream) {
     ADVGRPO_CHECK(image_embs && text_embs && loss && d_image_embs && B > 0 && P > 0, "clip_pair_loss: bad argument");
     hipStream_t s = as_stream(stream);
-    if (hipMemsetAsync(loss, 0, sizeof(float), s) != hipSuccess) { set_error("clip_pair_loss: memset failed"); return -2; }
-    hipLaunchKernelGGL(clip_pair_loss_kernel, dim3(B), dim3(64), 0, s, (const bf16_t*)image_embs, (const bf16_t*)text_embs,
+    hipLaunchKernelGGL(clip_pair_loss_kernel, dim3(1), dim3(64 * CLIP_LOSS_WAVES), 0, s, (const bf16_t*)image_embs, (const bf16_t*)text_embs,
                        B, P, logit_scale_exp, (const float*)nullptr, (const float*)nullptr, loss, (bf16_t*)d_image_embs);
     ADVGRPO_LAUNCH_CHECK();
     return 0;
@@ -213,8 +263,7 @@ extern "C" int advgrpo_clip_pair_loss_labels(const void* image_embs, const void*
     ADVGRPO_CHECK(image_embs && text_embs && loss && d_image_embs && B > 0 && P > 0, "clip_pair_loss_labels: bad argument");
     ADVGRPO_CHECK((label_0 == nullptr) == (label_1 == nullptr), "clip_pair_loss_labels: label_0 and label_1 come as a pair");
     hipStream_t s = as_stream(stream);
-    if (hipMemsetAsync(loss, 0, sizeof(float), s) != hipSuccess) { set_error("clip_pair_loss_labels: memset failed"); return -2; }
-    hipLaunchKernelGGL(clip_pair_loss_kernel, dim3(B), dim3(64), 0, s, (const bf16_t*)image_embs, (const bf16_t*)text_embs,
+    hipLaunchKernelGGL(clip_pair_loss_kernel, dim3(1), dim3(64 * CLIP_LOSS_WAVES), 0, s, (const bf16_t*)image_embs, (const bf16_t*)text_embs,
                        B, P, logit_scale_exp, label_0, label_1, loss, (bf16_t*)d_image_embs);
     ADVGRPO_LAUNCH_CHECK();
     return 0;
@@ -271,17 +320,22 @@ extern "C" int advgrpo_softmax_bwd_rows(const float* sc, const float* dp, void* 
 
 extern "C" int advgrpo_colsum_bf16(const void* x, int64_t ld, int R, int C, float* out, void* stream) {
     ADVGRPO_CHECK(x && out && R > 0 && C > 0, "colsum: bad argument");
-    hipLaunchKernelGGL(colsum_kernel, dim3((C + 255) / 256, (R + 63) / 64), dim3(256), 0, as_stream(stream),
-                       (const bf16_t*)x, ld, R, C, out);
+    hipLaunchKernelGGL(colsum_kernel, dim3((C + 63) / 64), dim3(64 * STRIP_WAVES), 0, as_stream(stream), (const bf16_t*)x, ld, R, C,
+                       out);
     ADVGRPO_LAUNCH_CHECK();
     return 0;
 }
 
+extern "C" int64_t advgrpo_ln_affine_grads_workspace_bytes(int M) { return M > 0 ? 2 * (int64_t)M * sizeof(float) : 0; }
+
 extern "C" int advgrpo_ln_affine_grads(const void* x, int64_t ldx, const void* dy, int64_t lddy, int M, int D, float eps,
-                                       float* grad_w, float* grad_b, void* stream) {
-    ADVGRPO_CHECK(x && dy && grad_w && grad_b && M > 0 && D > 0, "ln_affine_grads: bad argument");
-    hipLaunchKernelGGL(ln_affine_grads_kernel, dim3((M + 3) / 4), dim3(256), 0, as_stream(stream), (const bf16_t*)x, ldx,
-                       (const bf16_t*)dy, lddy, M, D, eps, grad_w, grad_b);
+                                       float* grad_w, float* grad_b, float* workspace, void* stream) {
+    ADVGRPO_CHECK(x && dy && grad_w && grad_b && workspace && M > 0 && D > 0, "ln_affine_grads: bad argument");
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(ln_row_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, ldx, M, D, eps, workspace);
+    ADVGRPO_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ln_affine_grads_kernel, dim3((D + 63) / 64), dim3(64 * STRIP_WAVES), 0, s, (const bf16_t*)x, ldx,
+                       (const bf16_t*)dy, lddy, M, D, workspace, grad_w, grad_b);
     ADVGRPO_LAUNCH_CHECK();
     return 0;
 }

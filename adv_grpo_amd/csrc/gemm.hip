@@ -323,12 +323,16 @@ static int gemm_prepare(GemmParams& p) {
     ADVGRPO_CHECK(p.splitk == 1 || (p.out_dtype == ADVGRPO_F32 && !p.bias && !p.gate && !p.residual && p.act == 0 &&
                                     !p.aux_out),
                   "gemm: split-K accumulates atomically into f32 and takes no other epilogue");
+    ADVGRPO_CHECK(!p.accumulate || (p.splitk == 1 && p.batch == 1 && !p.conv && p.out_dtype == ADVGRPO_F32 && !p.bias && !p.gate &&
+                                     !p.residual && p.act == 0 && !p.aux_out && !p.rms_w && !p.fp8),
+                  "gemm: accumulation into C is a plain f32 GEMM without other epilogue");
     ADVGRPO_CHECK(p.act < ACT_DGELU_TANH || p.aux_in, "gemm: d-activation epilogue needs aux_in");
     ADVGRPO_CHECK(!(p.aux_out || p.aux_in) || ((p.ld_aux & 3) == 0 && (p.N & 3) == 0), "gemm: aux needs N, ld_aux %% 4 == 0");
     int variant = gemm_variant(p.M, p.N, p.K, p.batch * p.splitk, p.conv, p.splitk == 1 && !p.conv);
 #ifdef ADVGRPO_EXPERIMENTS   // ADVGRPO_GEMM_FORCE_NK=N:K:variant overrides the tile variant of one Linear shape
     if (knobs().fn == p.N && knobs().fk == p.K && !p.conv && p.splitk == 1 && p.M >= 8192) variant = knobs().fv;
 #endif
+    if (variant == 30 && p.accumulate) variant = 15;   // (the eight-phase kernel has its own epilogue)
     if (variant == 30 && !gemm8p_ok(p)) variant = p.M >= 8192 && p.N >= 1024 ? 26 : 15;
     if (p.rms_w && (variant == 27 || variant == 1)) variant = 15;   // the fused QK-norm needs 64-wide wave tiles (one head per wave row)
     if (p.conv) {
@@ -478,6 +482,17 @@ extern "C" int advgrpo_gemm_bf16_train(const void* A, int64_t lda, const void* W
     p.residual = (const bf16_t*)residual; p.ldr = ldr;
     p.batch = 1; p.splitk = splitk < 1 ? 1 : splitk;
     p.aux_out = (bf16_t*)aux_out; p.aux_in = (const bf16_t*)aux_in; p.ld_aux = ld_aux;
+    return gemm_bf16(p, as_stream(stream));
+}
+
+/* C (f32) += alpha * A W^T, every element added by the one lane that owns it (no atomics: a fixed summation order) */
+extern "C" int advgrpo_gemm_bf16_acc_f32(const void* A, int64_t lda, const void* W, int64_t ldw, float* C, int64_t ldc, int M,
+                                         int N, int K, float alpha, void* stream) {
+    GemmParams p{};
+    p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.C = C;
+    p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.out_dtype = ADVGRPO_F32;
+    p.M = M; p.N = N; p.K = K; p.alpha = alpha;
+    p.batch = 1; p.splitk = 1; p.accumulate = 1;
     return gemm_bf16(p, as_stream(stream));
 }
 

@@ -30,6 +30,9 @@ struct GemmParams {
     // training extras: aux_out[orow, n] = pre-activation (bf16, pitch ldc); aux_in[orow, n] feeds the d-activation
     // epilogues; splitk > 1: the K range is split over grid.y and partial tiles are atomically added into f32 C
     bf16_t* aux_out; const bf16_t* aux_in; int64_t ld_aux; int splitk;
+    // accumulate (splitk == 1, f32 C, no other epilogue): C[m, n] += alpha * acc, read, added and written by the one lane that owns
+    // the element -- a fixed summation order, unlike the split-K atomics
+    int accumulate;
     // fused per-head RMSNorm on the first rms_nheads 64-wide column groups of the output (QK-norm of a fused QKV
     // projection: q heads then k heads, V untouched): y = bf16(bf16(x) * rsqrt(mean(x^2) + eps)) * w[(head / hpw), :];
     // rms_rs_out[orow, head] (f32, optional) keeps 1/rms for the backward.  Needs a 64-wide wave tile.

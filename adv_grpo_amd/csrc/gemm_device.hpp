@@ -286,7 +286,7 @@ __device__ __forceinline__ void gemm_epilogue_rows(const GemmParams& p, f32x4 (&
 // true when every operand of the epilogue can be accessed as aligned 16-byte row segments
 __device__ __forceinline__ bool epilogue_rows_ok(const GemmParams& p) {
     auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    return p.splitk == 1 && (p.N & 7) == 0 && ((p.ldc | p.ldr | p.gate_stride | p.ld_aux | p.strideC | p.strideR |
+    return p.splitk == 1 && !p.accumulate && (p.N & 7) == 0 && ((p.ldc | p.ldr | p.gate_stride | p.ld_aux | p.strideC | p.strideR |
                                                 p.gate_batch_stride) & 7) == 0 &&
            a16(p.C) && a16(p.bias) && a16(p.gate) && a16(p.residual) && a16(p.aux_out) && a16(p.aux_in);
 }
@@ -316,6 +316,20 @@ __device__ __forceinline__ void gemm_epilogue_frag(const GemmParams& p, f32x4 (&
         const int64_t o = (int64_t)bz * p.strideC + orow * p.ldc + n;
         const f32x4 a4 = acc[i][j];
         float v0 = a4[0] * p.alpha, v1 = a4[1] * p.alpha, v2 = a4[2] * p.alpha, v3 = a4[3] * p.alpha;
+        if (p.accumulate) {   // whole-K tile added into f32 C (gradient buffers) by its owner lane: no atomics, no other epilogue
+            float* c = reinterpret_cast<float*>(p.C) + o;
+            if (vec_ok && (reinterpret_cast<uintptr_t>(c) & 15) == 0) {
+                float4 q = *reinterpret_cast<const float4*>(c);
+                q.x += v0; q.y += v1; q.z += v2; q.w += v3;
+                *reinterpret_cast<float4*>(c) = q;
+            } else {
+                c[0] += v0;
+                if (n + 1 < p.N) c[1] += v1;
+                if (n + 2 < p.N) c[2] += v2;
+                if (n + 3 < p.N) c[3] += v3;
+            }
+            return;
+        }
         if (p.splitk > 1) {   // partial tile: f32 atomic accumulation (gradient buffers), no other epilogue
             float* c = reinterpret_cast<float*>(p.C) + o;
             unsafeAtomicAdd(c, v0);

@@ -455,12 +455,19 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const bf16_t* __restri
         *reinterpret_cast<uint4*>(out + (int64_t)row * D + d) = *reinterpret_cast<const uint4*>(src + d);
 }
 
-// per row: logit = h . w2 + b2 ; hinge loss / accuracy / d loss / d logit.  One wave per row.
-// stats[0] += loss, stats[1] += correct real cls, stats[2] += correct fake cls, stats[3] += sum(dl) (= d b2)
+// per row: logit = h . w2 + b2 ; hinge d loss / d logit.  One wave per row.
+// d_loss = 0.5*(mean_real relu(1-l) + mean_fake relu(1+l)) + patch_w * (same over patches)
+__device__ __forceinline__ float dino_row_weight(int row, int n, int Breal, int Btot, float patch_w, bool& real, bool& cls) {
+    const int b = row / (1 + n), j = row % (1 + n);
+    real = b < Breal;
+    cls = j == 0;
+    const int nb = real ? Breal : (Btot - Breal);
+    return cls ? 0.5f / (float)nb : patch_w * 0.5f / ((float)nb * (float)n);
+}
 __global__ __launch_bounds__(256) void dino_head_loss_kernel(const bf16_t* __restrict__ h, const bf16_t* __restrict__ w2,
                                                              const bf16_t* __restrict__ b2, int R, int Hd, int n, int Breal,
                                                              int Btot, float patch_w, float* __restrict__ logits,
-                                                             float* __restrict__ dl, float* __restrict__ stats) {
+                                                             float* __restrict__ dl) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= R) return;
@@ -469,43 +476,69 @@ __global__ __launch_bounds__(256) void dino_head_loss_kernel(const bf16_t* __res
     acc = wave_sum(acc);
     if (lane != 0) return;
     const float logit = round_bf16(acc + bf2f(b2[0]));
-    const int b = row / (1 + n), j = row % (1 + n);
-    const bool real = b < Breal, cls = j == 0;
+    bool real, cls;
+    const float wgt = dino_row_weight(row, n, Breal, Btot, patch_w, real, cls);
     const float y = real ? 1.f : -1.f;
-    const int nb = real ? Breal : (Btot - Breal);
-    // d_loss = 0.5*(mean_real relu(1-l) + mean_fake relu(1+l)) + patch_w * (same over patches)
-    const float wgt = cls ? 0.5f / (float)nb : patch_w * 0.5f / ((float)nb * (float)n);
     const float margin = 1.0f - y * logit;
-    const float g = margin > 0.f ? -y * wgt : 0.f;
     logits[row] = logit;
-    dl[row] = g;
-    atomicAdd(&stats[0], margin > 0.f ? margin * wgt : 0.f);
-    if (cls) atomicAdd(&stats[real ? 1 : 2], (y * logit > 0.f) ? 1.f : 0.f);
-    atomicAdd(&stats[3], g);
+    dl[row] = margin > 0.f ? -y * wgt : 0.f;
 }
 
-// dpre[r,c] = dl[r] * w2[c] * gelu_erf'(pre[r,c]) (bf16);  g_w2[c] += dl[r] * h[r,c];  g_b1[c] += dpre[r,c]
-__global__ __launch_bounds__(256) void dino_head_dpre_kernel(const bf16_t* __restrict__ pre, const bf16_t* __restrict__ h,
-                                                             const bf16_t* __restrict__ w2, const float* __restrict__ dl,
-                                                             bf16_t* __restrict__ dpre, float* __restrict__ g_w2,
-                                                             float* __restrict__ g_b1, int R, int Hd) {
-    // block = 256 columns x 32 rows
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= Hd) return;
-    const int r0 = blockIdx.y * 32, r1 = min(R, r0 + 32);
-    const float w = bf2f(w2[c]);
-    float sw = 0.f, sb = 0.f;
-    for (int r = r0; r < r1; ++r) {
-        const float u = bf2f(pre[(int64_t)r * Hd + c]);
-        const float d = dl[r];
-        const float dg = 0.5f * (1.0f + erff(u * 0.7071067811865476f)) + u * 0.3989422804014327f * __expf(-0.5f * u * u);
-        const float v = d * w * dg;
-        dpre[(int64_t)r * Hd + c] = f2bf(v);
-        sb += v;
-        sw += d * bf2f(h[(int64_t)r * Hd + c]);
+// stats[0] = loss, stats[1] = correct real cls, stats[2] = correct fake cls, stats[3] = sum(dl) (= d b2).  One workgroup:
+// thread t adds rows t, t + 256, ... in order, then block_sum (a fixed tree): the same bits on every run.
+__global__ __launch_bounds__(256) void dino_head_stats_kernel(const float* __restrict__ logits, const float* __restrict__ dl, int R,
+                                                              int n, int Breal, int Btot, float patch_w, float* __restrict__ stats) {
+    __shared__ float red[4];
+    float sl = 0.f, sr = 0.f, sf = 0.f, sd = 0.f;
+    for (int row = threadIdx.x; row < R; row += 256) {
+        bool real, cls;
+        const float wgt = dino_row_weight(row, n, Breal, Btot, patch_w, real, cls);
+        const float y = real ? 1.f : -1.f;
+        const float logit = logits[row];
+        const float margin = 1.0f - y * logit;
+        sl += margin > 0.f ? margin * wgt : 0.f;
+        if (cls && y * logit > 0.f) (real ? sr : sf) += 1.f;
+        sd += dl[row];
     }
-    atomicAdd(&g_w2[c], sw);
-    atomicAdd(&g_b1[c], sb);
+    sl = block_sum<4>(sl, red);
+    sr = block_sum<4>(sr, red);
+    sf = block_sum<4>(sf, red);
+    sd = block_sum<4>(sd, red);
+    if (threadIdx.x == 0) { stats[0] = sl; stats[1] = sr; stats[2] = sf; stats[3] = sd; }
+}
+
+// dpre[r,c] = dl[r] * w2[c] * gelu_erf'(pre[r,c]) (bf16);  g_w2[c] += dl[r] * h[r,c];  g_b1[c] += dpre[r,c] (the f32 value).
+// Column strips in a fixed order, as colsum_kernel (d_step_clip.hip): a workgroup owns 64 columns, wave w walks rows w, w + 16, ...
+constexpr int DPRE_WAVES = 16;
+__global__ __launch_bounds__(64 * DPRE_WAVES) void dino_head_dpre_kernel(const bf16_t* __restrict__ pre, const bf16_t* __restrict__ h,
+                                                                         const bf16_t* __restrict__ w2, const float* __restrict__ dl,
+                                                                         bf16_t* __restrict__ dpre, float* __restrict__ g_w2,
+                                                                         float* __restrict__ g_b1, int R, int Hd) {
+    __shared__ float part[2][DPRE_WAVES][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    float sw = 0.f, sb = 0.f;
+    if (c < Hd) {
+        const float w = bf2f(w2[c]);
+        for (int r = wv; r < R; r += DPRE_WAVES) {
+            const float u = bf2f(pre[(int64_t)r * Hd + c]);
+            const float d = dl[r];
+            const float dg = 0.5f * (1.0f + erff(u * 0.7071067811865476f)) + u * 0.3989422804014327f * __expf(-0.5f * u * u);
+            const float v = d * w * dg;
+            dpre[(int64_t)r * Hd + c] = f2bf(v);
+            sb += v;
+            sw += d * bf2f(h[(int64_t)r * Hd + c]);
+        }
+    }
+    part[0][wv][lane] = sw;
+    part[1][wv][lane] = sb;
+    __syncthreads();
+    if (wv == 0 && c < Hd) {
+        float tw = 0.f, tb = 0.f;
+        for (int k = 0; k < DPRE_WAVES; ++k) { tw += part[0][k][lane]; tb += part[1][k][lane]; }
+        g_w2[c] += tw;
+        g_b1[c] += tb;
+    }
 }
 
 }  // namespace advgrpo
@@ -526,10 +559,12 @@ extern "C" int advgrpo_dino_head_loss(const void* hidden, const void* w2, const 
     ADVGRPO_CHECK(hidden && w2 && b2 && logits && dlogits && stats4 && R == B_total * (1 + n) && B_real > 0 &&
                       B_total > B_real, "dino_head_loss: bad argument");
     hipStream_t s = advgrpo::as_stream(stream);
-    if (hipMemsetAsync(stats4, 0, 4 * sizeof(float), s) != hipSuccess) { advgrpo::set_error("memset failed"); return -2; }
     hipLaunchKernelGGL(advgrpo::dino_head_loss_kernel, dim3((R + 3) / 4), dim3(256), 0, s, (const advgrpo::bf16_t*)hidden,
                        (const advgrpo::bf16_t*)w2, (const advgrpo::bf16_t*)b2, R, Hd, n, B_real, B_total, patch_loss_weight,
-                       logits, dlogits, stats4);
+                       logits, dlogits);
+    ADVGRPO_LAUNCH_CHECK();
+    hipLaunchKernelGGL(advgrpo::dino_head_stats_kernel, dim3(1), dim3(256), 0, s, logits, dlogits, R, n, B_real, B_total,
+                       patch_loss_weight, stats4);
     ADVGRPO_LAUNCH_CHECK();
     return 0;
 }
@@ -537,7 +572,7 @@ extern "C" int advgrpo_dino_head_loss(const void* hidden, const void* w2, const 
 extern "C" int advgrpo_dino_head_dpre(const void* pre, const void* hidden, const void* w2, const float* dlogits, void* dpre,
                                       float* grad_w2, float* grad_b1, int R, int Hd, void* stream) {
     ADVGRPO_CHECK(pre && hidden && w2 && dlogits && dpre && grad_w2 && grad_b1 && R > 0 && Hd > 0, "dino_head_dpre: bad argument");
-    hipLaunchKernelGGL(advgrpo::dino_head_dpre_kernel, dim3((Hd + 255) / 256, (R + 31) / 32), dim3(256), 0,
+    hipLaunchKernelGGL(advgrpo::dino_head_dpre_kernel, dim3((Hd + 63) / 64), dim3(64 * advgrpo::DPRE_WAVES), 0,
                        advgrpo::as_stream(stream), (const advgrpo::bf16_t*)pre, (const advgrpo::bf16_t*)hidden,
                        (const advgrpo::bf16_t*)w2, dlogits, (advgrpo::bf16_t*)dpre, grad_w2, grad_b1, R, Hd);
     ADVGRPO_LAUNCH_CHECK();

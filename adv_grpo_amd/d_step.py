@@ -7,8 +7,9 @@ backbone features of the epoch's reference (real) and generated (fake) images, h
 
 Everything runs on the device: the reference's tensor -> PIL -> Resize(518, BICUBIC) -> ToTensor -> Normalize round
 trip (TD:135-149,166-176) is the bit-exact PIL-resample kernel with truncating uint8 quantisation; the two Linears
-are MFMA GEMMs (pre-activation kept for the backward), the first Linear's weight gradient is a split-K GEMM over the
-~12k feature rows, and all parameters / moments live in one flat f32 vector updated by one fused Adam launch.
+are MFMA GEMMs (pre-activation kept for the backward), the first Linear's weight gradient is a GEMM over the feature
+rows that adds into the f32 gradient in a fixed order, and all parameters / moments live in one flat f32 vector updated
+by one fused Adam launch.  No reduction of the D-step uses float atomics: two calls on the same input give the same bits.
 """
 import torch
 
@@ -93,7 +94,7 @@ class DinoHeadTrainable:
                                               gw2.data_ptr(), gb1.data_ptr(), R, self.Hd, _lib.stream_ptr()))
         gb2 += stats[3]
         # dW1 [Hd, D] += dpre^T X  (contraction over the R rows)
-        ops.gemm_train(ops.transpose(dpre), ops.transpose(X), out=gw1, splitk=max(1, min(16, R // 512)))
+        ops.gemm_train(ops.transpose(dpre), ops.transpose(X), out=gw1)
         d_loss = stats[0]
         acc = 0.5 * (stats[1] / B + stats[2] / B)
         return d_loss, acc

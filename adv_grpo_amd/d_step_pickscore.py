@@ -9,7 +9,8 @@ betas=(0.5, 0.999)) (TP:658).  ``ClipLastLayerTrainable``: the shipped ``tune_la
 CLIP pools the CLS token after the last layer, so for the trainable layer only the CLS row of its output matters:
 forward runs the frozen 31 layers with the regular encoder, then the last layer with full K/V but a single (CLS)
 query per image; the backward is the same structure reversed -- per-(image, head) single-query attention backward
-producing dq (CLS row), dk, dv (all 257 rows), weight gradients as split-K GEMMs over the token axis.
+producing dq (CLS row), dk, dv (all 257 rows), weight gradients as GEMMs over the token axis that add into the f32
+gradient vector in a fixed order (every reduction of the D-step is bitwise repeatable).
 
 DEVIATION (stated in SURVEY.md 2.2 / DESIGN.md): the discriminator gradients ARE all-reduced across ranks; the
 reference wraps the scorer in DDP but strips ``.module`` on the first reward call, so its ranks silently diverge.
@@ -106,29 +107,30 @@ class ClipLastLayerTrainable:
         T = ops.transpose
         colsum = lambda t, out: _lib.check(lib.advgrpo_colsum_bf16(t.data_ptr(), t.stride(0), t.shape[0], t.shape[1],
                                                                    out.data_ptr(), _lib.stream_ptr()))
+        ln_ws = torch.empty(lib.advgrpo_ln_affine_grads_workspace_bytes(M) // 4, dtype=f32, device=dev)
         ln_grads = lambda xx, dy, gw, gb: _lib.check(lib.advgrpo_ln_affine_grads(
             xx.data_ptr(), xx.stride(0), dy.data_ptr(), dy.stride(0), xx.shape[0], xx.shape[1], 1e-5, gw.data_ptr(),
-            gb.data_ptr(), _lib.stream_ptr()))
+            gb.data_ptr(), ln_ws.data_ptr(), _lib.stream_ptr()))
         ones = lambda w: (w.float() - 1.0).to(bf16).view(1, -1)                      # LN affine as a "(1 + scale)" modulation
         dpooled = ops.gemm(de, T(m.v_proj, pad_to=8))                                # de . Wproj -> [Bt, D]
         dx2 = ops.layernorm_mod_bwd(x2, dpooled, scale0=ones(m.post_ln[0]), rows_per_batch=Bt, eps=1e-5)
         # MLP
-        ops.gemm_train(T(dx2), T(mid), out=g("fc2.w"), splitk=2)                     # dW2 = dx2^T mid
+        ops.gemm_train(T(dx2), T(mid), out=g("fc2.w"))                               # dW2 = dx2^T mid
         colsum(dx2, g("fc2.b"))
         dpre = ops.gemm_train(dx2, T(L["fc2.w"], pad_to=8), act="dgelu", aux_in=pre)
-        ops.gemm_train(T(dpre), T(h2), out=g("fc1.w"), splitk=2)
+        ops.gemm_train(T(dpre), T(h2), out=g("fc1.w"))
         colsum(dpre, g("fc1.b"))
         dh2 = ops.gemm(dpre, T(L["fc1.w"], pad_to=8))
         ln_grads(x1, dh2, g("ln2.w"), g("ln2.b"))
         dx1 = ops.layernorm_mod_bwd(x1, dh2, scale0=ones(L["ln2.w"]), dres=dx2, rows_per_batch=Bt, eps=1e-5)
         # attention output projection
-        ops.gemm_train(T(dx1), T(o_cls), out=g("out.w"), splitk=2)
+        ops.gemm_train(T(dx1), T(o_cls), out=g("out.w"))
         colsum(dx1, g("out.b"))
         do_cls = ops.gemm(dx1, T(L["out.w"], pad_to=8))
         dqkv = torch.empty(M, 3 * D, dtype=bf16, device=dev)
         _lib.check(lib.advgrpo_cls_attention_bwd(qkv.data_ptr(), probs.data_ptr(), do_cls.data_ptr(), dqkv.data_ptr(), Bt, S,
                                                  H, hd, hd ** -0.5, _lib.stream_ptr()))
-        ops.gemm_train(T(dqkv), T(h1), out=g("qkv.w"), splitk=16)                    # contraction over all M tokens
+        ops.gemm_train(T(dqkv), T(h1), out=g("qkv.w"))                               # contraction over all M tokens
         colsum(dqkv, g("qkv.b"))
         dh1 = ops.gemm(dqkv, T(L["qkv.w"], pad_to=8))
         ln_grads(x, dh1, g("ln1.w"), g("ln1.b"))
@@ -262,31 +264,31 @@ class ClipLayersTrainable(ClipLastLayerTrainable):
         T = ops.transpose
         colsum = lambda t, out: _lib.check(lib.advgrpo_colsum_bf16(t.data_ptr(), t.stride(0), t.shape[0], t.shape[1],
                                                                    out.data_ptr(), _lib.stream_ptr()))
+        ln_ws = torch.empty(lib.advgrpo_ln_affine_grads_workspace_bytes(M) // 4, dtype=f32, device=dev)
         ln_grads = lambda xx, dy, gw, gb: _lib.check(lib.advgrpo_ln_affine_grads(
             xx.data_ptr(), xx.stride(0), dy.data_ptr(), dy.stride(0), xx.shape[0], xx.shape[1], 1e-5, gw.data_ptr(),
-            gb.data_ptr(), _lib.stream_ptr()))
+            gb.data_ptr(), ln_ws.data_ptr(), _lib.stream_ptr()))
         ones = lambda w: (w.float() - 1.0).to(bf16).view(1, -1)
         dpooled = ops.gemm(de, T(m.v_proj, pad_to=8))
         dcls = ops.layernorm_mod_bwd(x_cls, dpooled, scale0=ones(m.post_ln[0]), rows_per_batch=Bt, eps=1e-5)
         dx = torch.zeros(M, D, dtype=bf16, device=dev)                          # only the CLS rows of the last layer's output carry gradient
         dx.view(Bt, S, D)[:, 0] = dcls
-        sk = max(1, min(16, ((M + 63) // 64)))                                     # split-K slices of the token-contracted weight gradients
         for li in reversed(range(self.k)):
             L, s = self.layers[li], saved[li]
             g = lambda n: self.view(self.grads, (li, n))
-            ops.gemm_train(T(dx), T(s["mid"]), out=g("fc2.w"), splitk=sk)
+            ops.gemm_train(T(dx), T(s["mid"]), out=g("fc2.w"))
             colsum(dx, g("fc2.b"))
             dpre = ops.gemm_train(dx, T(L["fc2.w"], pad_to=8), act="dgelu", aux_in=s["pre"])
-            ops.gemm_train(T(dpre), T(s["h2"]), out=g("fc1.w"), splitk=sk)
+            ops.gemm_train(T(dpre), T(s["h2"]), out=g("fc1.w"))
             colsum(dpre, g("fc1.b"))
             dh2 = ops.gemm(dpre, T(L["fc1.w"], pad_to=8))
             ln_grads(s["x1"], dh2, g("ln2.w"), g("ln2.b"))
             dx1 = ops.layernorm_mod_bwd(s["x1"], dh2, scale0=ones(L["ln2.w"]), dres=dx, rows_per_batch=M, eps=1e-5)
-            ops.gemm_train(T(dx1), T(s["o"]), out=g("out.w"), splitk=sk)
+            ops.gemm_train(T(dx1), T(s["o"]), out=g("out.w"))
             colsum(dx1, g("out.b"))
             d_o = ops.gemm(dx1, T(L["out.w"], pad_to=8))
             dqkv = self._attention_bwd(s["qkv"], d_o, Bt, S, H, hd)
-            ops.gemm_train(T(dqkv), T(s["h1"]), out=g("qkv.w"), splitk=sk)
+            ops.gemm_train(T(dqkv), T(s["h1"]), out=g("qkv.w"))
             colsum(dqkv, g("qkv.b"))
             dh1 = ops.gemm(dqkv, T(L["qkv.w"], pad_to=8))
             ln_grads(s["x_in"], dh1, g("ln1.w"), g("ln1.b"))

@@ -798,12 +798,19 @@ ACT_D = {"dgelu_tanh": 5, "dgelu": 6, "mul_aux": 7}   # "mul_aux": y *= aux_in (
 def gemm_train(a, w, bias=None, act=None, alpha=1.0, gate=None, gate_rows=0, residual=None, out=None,
                out_dtype=torch.bfloat16, aux_out=None, aux_in=None, splitk=1, M=None):
     """GEMM with the training extras (see advgrpo_gemm_bf16_train): aux_out = pre-activation copy,
-    act in {"dgelu_tanh","dgelu"} multiplies by the activation derivative at aux_in, splitk > 1 accumulates
-    atomically into an f32 `out` (which must be given and hold the running sum)."""
+    act in {"dgelu_tanh","dgelu"} multiplies by the activation derivative at aux_in.  An f32 `out` holding a running sum
+    is accumulated into: with splitk == 1 in a fixed order (advgrpo_gemm_bf16_acc_f32, bitwise repeatable), with splitk > 1
+    by the split-K atomics (faster for a long contraction, last bits vary from run to run)."""
     lib = _lib.load()
     K = a.shape[1]
     M = a.shape[0] if M is None else M
     N = w.shape[0]
+    if out is not None and out.dtype == torch.float32 and splitk == 1:
+        assert bias is None and act is None and gate is None and residual is None and aux_out is None and aux_in is None
+        with _Prof(M, N, K, 1, 0):
+            _lib.check(lib.advgrpo_gemm_bf16_acc_f32(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(),
+                                                     out.stride(0), M, N, K, float(alpha), _lib.stream_ptr()))
+        return out
     if out is None:
         assert splitk == 1
         out = torch.empty(M, N, dtype=out_dtype, device=a.device)

@@ -561,12 +561,17 @@ int advgrpo_gemm_fp8_grouped(const advgrpo_gemm_desc* descs, const advgrpo_fp8_s
  * transformer call inside compute_log_prob (TP:233-267) is assembled from these + advgrpo_attention_bwd. */
 /* GEMM with training extras: aux_out[orow,n] = pre-activation (bf16, pitch ld_aux); act 5/6 = multiply by
  * GELU-tanh' / GELU-erf' evaluated at aux_in[orow,n]; splitk > 1: contraction split over workgroups, partial
- * tiles atomically added into an f32 C (LoRA weight gradients, whose contraction runs over all tokens). */
+ * tiles atomically added into an f32 C (the order of those additions is not fixed, so the last bits vary from run to run;
+ * advgrpo_gemm_bf16_acc_f32 below accumulates in a fixed order). */
 int advgrpo_gemm_bf16_train(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
                             int out_dtype, int M, int N, int K, const void* bias, int act, float alpha,
                             const void* gate, int64_t gate_stride, int gate_rows, const void* residual,
                             int64_t ldr, void* aux_out, const void* aux_in, int64_t ld_aux, int splitk,
                             void* stream);
+/* C (f32, pitch ldc) += alpha * A W^T over the whole K range.  Every element of C is read, added and written by the one
+ * lane that owns it, so unlike split-K the result is bitwise repeatable (the D-steps' weight gradients). */
+int advgrpo_gemm_bf16_acc_f32(const void* A, int64_t lda, const void* W, int64_t ldw, float* C, int64_t ldc, int M, int N,
+                              int K, float alpha, void* stream);
 /* Token-contracted GEMM for the LoRA weight gradients (PEFT LoRA layers set up at TP:490-511, differentiated by
  * loss.backward() at TP:1165): C[n1,n2] += alpha * sum_m P[row_p(m), n1] * Q[row_q(m), n2], f32 atomic accumulation;
  * P [M, N1] and Q [M, 64] bf16, token-major, rows through the (seg_rows, seg_stride, seg_off) map; transpose_out
@@ -657,14 +662,15 @@ int advgrpo_ema_step(float* ema, const float* param, int64_t n, float one_minus_
  * train_dino (scripts/train_sd3_fast_dino_patch.py:156-232) on frozen-backbone features: hinge loss on the CLS logit
  * + 0.3 x hinge on n sampled patch logits; head = Linear(D,Hd) -> GELU -> Linear(Hd,1) (TD:592-603).
  * Rows are [cls, n patches] per image, B_real real images first.  The two Linears run on advgrpo_gemm_bf16_train
- * (pre-activation kept), these kernels do the rest; weight gradients of the first Linear are a split-K GEMM. */
+ * (pre-activation kept), these kernels do the rest; the first Linear's weight gradient is advgrpo_gemm_bf16_acc_f32. */
 int advgrpo_gather_rows(const void* feats, const int64_t* idx, void* out, int B, int T, int D, int n, void* stream);
 /* logits[r] = hidden[r,:].w2 + b2; dlogits = d loss / d logit; stats4 = {loss, #real cls correct, #fake cls correct,
  * sum(dlogits) = grad b2}. */
 int advgrpo_dino_head_loss(const void* hidden, const void* w2, const void* b2, int R, int Hd, int n, int B_real,
                            int B_total, float patch_loss_weight, float* logits, float* dlogits, float* stats4,
                            void* stream);
-/* dpre = dlogits (x) w2 * GELU'(pre) (bf16); grad_w2[c] += sum_r dlogits[r] hidden[r,c]; grad_b1[c] += sum_r dpre[r,c]. */
+/* dpre = dlogits (x) w2 * GELU'(pre) (bf16); grad_w2[c] += sum_r dlogits[r] hidden[r,c]; grad_b1[c] += sum_r dpre[r,c].
+ * Both kernels sum in a fixed order (no float atomics): stats4 and the gradients are bitwise repeatable. */
 int advgrpo_dino_head_dpre(const void* pre, const void* hidden, const void* w2, const float* dlogits, void* dpre,
                            float* grad_w2, float* grad_b1, int R, int Hd, void* stream);
 
@@ -693,9 +699,13 @@ int advgrpo_clip_pair_loss_labels(const void* image_embs, const void* text_embs,
  * index r % n >= n_valid) and columns come out zero. */
 int advgrpo_softmax_bwd_rows(const float* sc, const float* dp, void* p16, void* ds16, int64_t rows, int n, int n_valid, float scale,
                              void* stream);
+/* Bias / LayerNorm-affine gradients.  Each column is summed over the rows in a fixed order (no float atomics): the result is
+ * bitwise repeatable.  ln_affine_grads: workspace = advgrpo_ln_affine_grads_workspace_bytes(M) bytes of device memory (per-row
+ * mean and 1/std). */
 int advgrpo_colsum_bf16(const void* x, int64_t ld, int R, int C, float* out /* += */, void* stream);
+int64_t advgrpo_ln_affine_grads_workspace_bytes(int M);
 int advgrpo_ln_affine_grads(const void* x, int64_t ldx, const void* dy, int64_t lddy, int M, int D, float eps,
-                            float* grad_w /* += */, float* grad_b /* += */, void* stream);
+                            float* grad_w /* += */, float* grad_b /* += */, float* workspace, void* stream);
 
 /* ------------------------------------------------------------------ JPEG (compressibility reward)
  * Baseline sequential JPEG of every image, byte-exact with PIL.Image.save(format="JPEG", quality=quality) (Pillow /
