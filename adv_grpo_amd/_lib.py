@@ -230,6 +230,7 @@ SIGNATURES = {
     "advgrpo_jpeg_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "advgrpo_jpeg_max_file_bytes": (c_int64, [c_int, c_int]),
     "advgrpo_jpeg_encode": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, c_int64, _P]),
+    "advgrpo_siglip_preprocess_patches": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, _P]),
 }
 
 

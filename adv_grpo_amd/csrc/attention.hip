@@ -26,13 +26,15 @@
 namespace advgrpo {
 
 
-// HD = 64 (MMDiT, DINOv2, CLIP text) or 80 (CLIP ViT-H vision: 1280 / 16 heads).  For HD = 80 the
-// QK^T contraction is padded to 96 with zero columns in LDS (K) and zero Q fragments.
+// HD = 64 (MMDiT, DINOv2, CLIP text), 72 (SigLIP so400m/14: 1152 / 16 heads) or 80 (CLIP ViT-H vision: 1280 / 16 heads).  For
+// HD = 72 / 80 the QK^T contraction is padded to 96 with zero columns in LDS (K) and zero Q fragments.  For HD = 72 the PV product
+// runs over 80 columns (zero V columns 72..79 in LDS) and the epilogue stores exactly the head's 72 columns: the output is packed
+// [.., H * 72], so a wider store would overwrite the next head.
 template <int HD>
 __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttnParams p) {
-    static_assert(HD == 64 || HD == 80, "head dim 64 or 80");
+    static_assert(HD == 64 || HD == 72 || HD == 80, "head dim 64, 72 or 80");
     constexpr int KS = (HD + 31) / 32;          // 32-deep MFMA steps over d
-    constexpr int DB = HD / 16;                 // 16-wide output blocks over d
+    constexpr int DB = (HD + 15) / 16;          // 16-wide output blocks over d (the last one half padding for HD = 72)
     constexpr int ATT_PITCH = KS * 32 + 8;      // LDS row pitch in elements: 144 B / 208 B, odd multiple of 16 B
     constexpr int CPR = HD / 8;                 // 16-byte chunks per row
     constexpr int NCH = (ATT_KB * CPR + 255) / 256;  // staging chunks per thread
@@ -95,6 +97,12 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttnParams p) 
         for (int i = tid; i < 2 * ATT_KB * (KS * 32 - HD) / 8; i += 256) {
             const int row = i / ((KS * 32 - HD) / 8), cc = i % ((KS * 32 - HD) / 8);
             *reinterpret_cast<uint4*>(Ks + row * ATT_PITCH + HD + cc * 8) = uint4{0, 0, 0, 0};
+        }
+    }
+    if constexpr (DB * 16 != HD) {  // ... and the padded V columns (read by the last output block, never stored)
+        for (int i = tid; i < 2 * ATT_KB * (DB * 16 - HD) / 8; i += 256) {
+            const int row = i / ((DB * 16 - HD) / 8), cc = i % ((DB * 16 - HD) / 8);
+            *reinterpret_cast<uint4*>(Vs + row * ATT_PITCH + HD + cc * 8) = uint4{0, 0, 0, 0};
         }
     }
 
@@ -228,6 +236,7 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttnParams p) 
         bf16_t* op = p.o + (int64_t)b * p.bso + (int64_t)qi * p.ldo + h * HD + g * 4;
 #pragma unroll
         for (int db = 0; db < DB; ++db) {
+            if (db * 16 + g * 4 >= HD) continue;     // HD = 72: lanes g >= 2 of the last block hold padding columns
             const f32x4 v = o[db][qb] * inv;
             uint2 pk;
             pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
@@ -737,7 +746,8 @@ __global__ __launch_bounds__(256, ATT_WGS) void attention_fwd_glds_kernel(const 
 
 int attention_fwd(const AttnParams& p_in, int B, int head_dim, hipStream_t s) {
     AttnParams p = p_in;
-    ADVGRPO_CHECK(head_dim == 64 || head_dim == 80 || head_dim == 128, "attention: head_dim %d not supported (64, 80, 128)", head_dim);
+    ADVGRPO_CHECK(head_dim == 64 || head_dim == 72 || head_dim == 80 || head_dim == 128, "attention: head_dim %d not supported (64, 72, 80, 128)",
+                  head_dim);
     ADVGRPO_CHECK(p.q && p.k && p.v && p.o, "attention: null pointer");
     ADVGRPO_CHECK(p.Sq > 0 && p.Skv > 0 && p.H > 0 && B > 0, "attention: bad shape");
     ADVGRPO_CHECK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldo % 4 == 0,
@@ -767,6 +777,9 @@ int attention_fwd(const AttnParams& p_in, int B, int head_dim, hipStream_t s) {
     if (head_dim == 64 && use_glds && o16 && p.bias) hipLaunchKernelGGL(attention_fwd_glds_kernel<true>, grid, dim3(256), 0, s, p);
     else if (head_dim == 64 && use_glds && o16) hipLaunchKernelGGL(attention_fwd_glds_kernel<false>, grid, dim3(256), 0, s, p);
     else if (head_dim == 64) hipLaunchKernelGGL(attention_fwd_kernel<64>, grid, dim3(256), 0, s, p);
+    // the SigLIP so400m/14 tower (729 tokens, 16 heads x 72; its K / V of 210 KB per head do not fit in LDS) and its attention-pooling
+    // head (one probe query, q batch stride 0): the tiled kernel streams K / V in 64-key tiles
+    else if (head_dim == 72) hipLaunchKernelGGL(attention_fwd_kernel<72>, grid, dim3(256), 0, s, p);
     else if (use_resident && !p.causal && !p.bias && p.Skv <= RES_MAXT * ATT_KB && p.Sq <= RES_MAX_SQ && (int64_t)2 * p.H * B < (1ll << 31))
         return attention_fwd_resident_launch(p, B, s);       // the CLIP ViT-H vision tower (257 tokens): K / V of a head resident in LDS
     else hipLaunchKernelGGL(attention_fwd_kernel<80>, grid, dim3(256), 0, s, p);

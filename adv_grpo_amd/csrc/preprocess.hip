@@ -11,6 +11,7 @@
 //     uint8 intermediate) after the reference's (x*255).round().clamp() quantisation.
 //   * DINO path: torch's upsample_bicubic2d (A = -0.75, align_corners=False, no antialias) in f32 on
 //     bf16 inputs, rounded to bf16, then (x - mean)/std in f32, rounded to bf16.
+//   * SigLIP path: the same resize in the input's own dtype (no bf16 rounding of f32 / u8 inputs), (x - 0.5)/0.5 in f32, bf16.
 //   * reward epilogues: gather + L2-normalise the CLS / sampled patch tokens, head second layer +
 //     0.7/0.3 mix (rewards.py:399-421); PickScore exp(logit_scale) * cos / 26 (pickscore_scorer.py:40-52).
 #include "common.hpp"
@@ -86,7 +87,9 @@ __global__ void clip_resize_v_patches_kernel(const uint8_t* __restrict__ tmp, bf
     }
 }
 
-// ---- DINO: bicubic (A=-0.75) resize in f32 from (bf16-rounded) inputs -> bf16 -> normalise -> im2col
+// ---- DINO / SigLIP: torch's upsample_bicubic2d (A = -0.75, align_corners=False, no antialias) in f32 -> normalise -> im2col.
+// Same tap formulas as torch; the f32 sums may round differently from torch's build (summation order / contraction), which moves
+// a bf16 result by one ulp on a few 1e-5 of the pixels (tests/test_gpu_vit.py, tests/test_gpu_siglip.py).
 __device__ inline void cubic_coeffs(float t, float c[4]) {
     const float A = -0.75f;
     const float x1 = t + 1.0f, x2 = t, x3 = 1.0f - t, x4 = 2.0f - t;
@@ -95,11 +98,27 @@ __device__ inline void cubic_coeffs(float t, float c[4]) {
     c[2] = ((A + 2.0f) * x3 - (A + 3.0f)) * x3 * x3 + 1.0f;
     c[3] = ((A * x4 - 5.0f * A) * x4 + 8.0f * A) * x4 - 4.0f * A;
 }
-// X3 (the fp32 tower of image_similarity_score, rewards.py:147-203): no bf16 rounding anywhere, the normalised pixel leaves as
-// the split-bf16 left operand [hi | hi | lo], row pitch 3 * 640
-template <bool X3>
-__global__ void dino_preprocess_patches_kernel(const void* __restrict__ img, int dt, bf16_t* __restrict__ patches, int B,
-                                               int H, int W, int OH, int OW, float3 mean, float3 stdv) {
+
+// The three preprocessors share one resize body and differ in where they round to bf16:
+//   DINO      (bf16 tower, rewards.py:379-391): inputs rounded to bf16 first (the reference casts images to bf16, TP:816), the resize
+//             result rounded to bf16, (x - mean) / std in f32, bf16.
+//   DINO_X3   (the fp32 tower of image_similarity_score, rewards.py:147-203): no bf16 rounding anywhere; the normalised pixel leaves as
+//             the split-bf16 left operand [hi | hi | lo], row pitch 3 * 640.
+//   SIGLIP    (siglip_image_similarity, rewards.py:87-115): F.interpolate in the input's dtype -- a bf16 input's resize result is
+//             rounded to bf16, an f32 one is not; u8 inputs are x * (1 / 255) in f32 first (torch's division of a device tensor by a
+//             python number) -- then (x - 0.5) / 0.5 in f32, bf16.  The image is resized to OH x OW = 384 x 384, but the 14/14 patch
+//             conv reads only the top-left (384 / 14) * 14 rows and columns: those are the only pixels computed.
+enum PreMode { PRE_DINO = 0, PRE_DINO_X3 = 1, PRE_SIGLIP = 2 };
+
+__device__ inline float ld_img_u8(const void* img, int dt, int64_t i) {
+    if (dt == ADVGRPO_U8) return (float)reinterpret_cast<const uint8_t*>(img)[i] * (1.0f / 255.0f);
+    return ld_img(img, dt, i);
+}
+
+template <int MODE>
+__global__ void bicubic_patches_kernel(const void* __restrict__ img, int dt, bf16_t* __restrict__ patches, int B, int H, int W, int OH,
+                                       int OW, float3 mean, float3 stdv) {
+    constexpr bool X3 = MODE == PRE_DINO_X3;
     const int gw = OW / PATCH;
     const int P = (OH / PATCH) * gw;
     const float sy = (float)H / (float)OH, sx = (float)W / (float)OW;
@@ -130,13 +149,19 @@ __global__ void dino_preprocess_patches_kernel(const void* __restrict__ img, int
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
                 const int xx = min(max(x0 - 1 + d, 0), W - 1);
-                float v = ld_img(img, dt, base + (int64_t)yy * W + xx);
-                if (!X3 && dt != ADVGRPO_BF16) v = round_bf16(v);   // the reference casts images to bf16 first (TP:816)
+                float v;
+                if constexpr (MODE == PRE_SIGLIP) {
+                    v = ld_img_u8(img, dt, base + (int64_t)yy * W + xx);
+                } else {
+                    v = ld_img(img, dt, base + (int64_t)yy * W + xx);
+                    if (!X3 && dt != ADVGRPO_BF16) v = round_bf16(v);
+                }
                 r += cx[d] * v;
             }
             acc += cy[a] * r;
         }
-        const float rb = X3 ? acc : round_bf16(acc);
+        const bool round_resized = MODE == PRE_DINO || (MODE == PRE_SIGLIP && dt == ADVGRPO_BF16);
+        const float rb = round_resized ? round_bf16(acc) : acc;
         const float m = c == 0 ? mean.x : (c == 1 ? mean.y : mean.z);
         const float s = c == 0 ? stdv.x : (c == 1 ? stdv.y : stdv.z);
         const float v = (rb - m) / s;
@@ -259,10 +284,10 @@ static int dino_preprocess_impl(bool x3, const void* image, int image_dtype, voi
     const float3 m = make_float3(mean3_host[0], mean3_host[1], mean3_host[2]);
     const float3 sd = make_float3(std3_host[0], std3_host[1], std3_host[2]);
     if (x3)
-        hipLaunchKernelGGL(dino_preprocess_patches_kernel<true>, dim3(4096), dim3(256), 0, as_stream(stream), image, image_dtype,
+        hipLaunchKernelGGL(bicubic_patches_kernel<PRE_DINO_X3>, dim3(4096), dim3(256), 0, as_stream(stream), image, image_dtype,
                            (bf16_t*)patches, B, H, W, OH, OW, m, sd);
     else
-        hipLaunchKernelGGL(dino_preprocess_patches_kernel<false>, dim3(4096), dim3(256), 0, as_stream(stream), image, image_dtype,
+        hipLaunchKernelGGL(bicubic_patches_kernel<PRE_DINO>, dim3(4096), dim3(256), 0, as_stream(stream), image, image_dtype,
                            (bf16_t*)patches, B, H, W, OH, OW, m, sd);
     ADVGRPO_LAUNCH_CHECK();
     return 0;
@@ -279,6 +304,19 @@ extern "C" int advgrpo_dino_preprocess_patches_x3(const void* image, int image_d
                                                   int OH, int OW, const float* mean3_host, const float* std3_host,
                                                   void* stream) {
     return dino_preprocess_impl(true, image, image_dtype, patches3, B, H, W, OH, OW, mean3_host, std3_host, stream);
+}
+
+/* siglip_image_similarity's preprocessing (see the kernel): image [B,3,H,W] f32 / bf16 / u8 -> patches bf16 [B*P, 640], P = (OS/14)^2 */
+extern "C" int advgrpo_siglip_preprocess_patches(const void* image, int image_dtype, void* patches, int B, int H, int W, int OS,
+                                                 void* stream) {
+    ADVGRPO_CHECK(image && patches, "siglip_preprocess: null pointer");
+    ADVGRPO_CHECK(B > 0 && H > 0 && W > 0 && OS >= PATCH, "siglip_preprocess: bad shape (B=%d H=%d W=%d OS=%d)", B, H, W, OS);
+    ADVGRPO_CHECK(image_dtype == ADVGRPO_F32 || image_dtype == ADVGRPO_BF16 || image_dtype == ADVGRPO_U8,
+                  "siglip_preprocess: image dtype must be f32, bf16 or u8");
+    hipLaunchKernelGGL(bicubic_patches_kernel<PRE_SIGLIP>, dim3(4096), dim3(256), 0, as_stream(stream), image, image_dtype,
+                       (bf16_t*)patches, B, H, W, OS, OS, make_float3(0.5f, 0.5f, 0.5f), make_float3(0.5f, 0.5f, 0.5f));
+    ADVGRPO_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int advgrpo_gather_l2norm_rows(const void* feats, const int64_t* idx, void* out, int B, int T, int D, int n,

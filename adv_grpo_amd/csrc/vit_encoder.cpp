@@ -4,7 +4,8 @@
 // lived in Python (adv_grpo_amd/vit.py: _Encoder.__call__).  This file is that order in C++ for the whole stack: CLIP ViT-H/14's 32 vision
 // layers and 24 causal text layers (transformers' CLIPEncoderLayer behind CLIPModel.get_image_features / get_text_features,
 // adv_grpo/pickscore_scorer.py:40-44, adv_grpo/pick_score_training.py:95-106) and DINOv2 ViT-B/14's 12 blocks with LayerScale (timm's
-// forward_features, adv_grpo/rewards.py:397, scripts/train_sd3_fast_dino_patch.py:183-184).  Per layer, on the caller's stream:
+// forward_features, adv_grpo/rewards.py:397, scripts/train_sd3_fast_dino_patch.py:183-184) and SigLIP so400m/14's 27 layers (transformers'
+// SiglipEncoderLayer behind siglip_image_similarity, adv_grpo/rewards.py:69-144; head dim 72).  Per layer, on the caller's stream:
 //   1  h = LayerNorm(x) (affine)                     2  qkv = h Wqkv^T + b            (q | k | v packed along N)
 //   3  o = softmax(q k^T / sqrt(d) [causal]) v       4  x += [ls1 *] (o Wo^T + b)      (residual -- and LayerScale as the gate operand -- in the epilogue)
 //   5  h = LayerNorm(x)                              6  m = act(h W1^T + b)            7  x += [ls2 *] (m W2^T + b)
@@ -28,7 +29,8 @@ extern "C" int advgrpo_vit_forward(const advgrpo_vit_desc* dsc, void* workspace,
     ADVGRPO_CHECK(B > 0 && S > 0 && D > 0 && H > 0 && F > 0 && D % H == 0 && d.n_layers >= 0 && d.x && (d.layers || d.n_layers == 0),
                   "vit_forward: bad descriptor (B=%d S=%d D=%d H=%d mlp=%d layers=%d)", B, S, D, H, F, d.n_layers);
     const int hd = D / H;
-    ADVGRPO_CHECK(hd == 64 || hd == 80, "vit_forward: head dim %d (the towers on this path have 64: DINOv2-B, CLIP text; 80: CLIP ViT-H)", hd);
+    ADVGRPO_CHECK(hd == 64 || hd == 72 || hd == 80,
+                  "vit_forward: head dim %d (the towers on this path have 64: DINOv2-B, CLIP text; 72: SigLIP so400m; 80: CLIP ViT-H)", hd);
     ADVGRPO_CHECK(workspace_bytes >= advgrpo_vit_workspace_bytes(B, S, D, F) && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
                   "vit_forward: workspace too small or not 256-byte aligned");
     const int M = B * S;
@@ -38,7 +40,7 @@ extern "C" int advgrpo_vit_forward(const advgrpo_vit_desc* dsc, void* workspace,
     char* qkv = take((int64_t)M * 3 * D);
     char* o = take((int64_t)M * D);
     char* m = take((int64_t)M * F);
-    const float scale = 1.0f / sqrtf((float)hd);
+    const float scale = (float)(1.0 / sqrt((double)hd));     // = float(hd ** -0.5), the Python sequencing's scale (1.0f / sqrtf(72.f) is 1 ulp off)
     int rc;
     for (int l = 0; l < d.n_layers; ++l) {
         const advgrpo_vit_layer& L = d.layers[l];

@@ -18,7 +18,8 @@ cache, or a ``save_pretrained`` directory) and
 
 Layout read (diffusers ``model_index.json`` pipelines):  ``transformer/`` ``vae/`` ``text_encoder/`` ``text_encoder_2/`` ``text_encoder_3/``
 each with ``config.json`` + ``diffusion_pytorch_model[.fp16].safetensors`` | ``model[.fp16].safetensors`` | ``<stem>.safetensors.index.json`` +
-shards.  Scorers: a ``CLIPModel`` directory (``config.json`` + ``model.safetensors``) and a timm directory (``config.json`` with
+shards.  Scorers: a ``CLIPModel`` directory (``config.json`` + ``model.safetensors``), a ``SiglipModel`` / ``SiglipVisionModel`` directory
+and a timm directory (``config.json`` with
 ``architecture`` + ``model.safetensors``).  ``pytorch_model.bin`` pickles are read with ``torch.load(weights_only=True)`` when no safetensors
 file exists.  Tested on synthetic snapshots written in exactly this layout (tests/test_hub.py); no released checkpoint exists in this image.
 """
@@ -29,8 +30,8 @@ import os
 import torch
 
 from . import synthetic
-from .model_configs import (ClipConfig, ClipTextConfig, DinoConfig, MMDiTConfig, QwenMMDiTConfig, QwenTextConfig, QwenVaeConfig, T5Config,
-                            VaeConfig)
+from .model_configs import (ClipConfig, ClipTextConfig, DinoConfig, MMDiTConfig, QwenMMDiTConfig, QwenTextConfig, QwenVaeConfig,
+                            SiglipVisionConfig, T5Config, VaeConfig)
 
 
 class HubError(RuntimeError):
@@ -303,6 +304,52 @@ def load_timm_dinov2(model_dir):
     want = synthetic.shapes(synthetic.dino_weights, out)
     validate(header_shapes(model_dir), want, model_dir)
     return read_tensors(model_dir, keys=set(want)), out
+
+
+# transformers' SiglipVisionConfig defaults: a config.json written by save_pretrained omits the fields left at them
+_SIGLIP_VISION_DEFAULTS = dict(hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12, num_channels=3,
+                               image_size=224, patch_size=16, hidden_act="gelu_pytorch_tanh", layer_norm_eps=1e-6)
+
+
+def _siglip_rename(k):
+    """SiglipModel keys as they are; a SiglipVisionModel saved by transformers 5 drops the ``vision_model.`` prefix; the text tower and the
+    contrastive logit scale / bias are not part of the image-similarity reward."""
+    if k.startswith("text_model.") or k in ("logit_scale", "logit_bias"):
+        return None
+    return k if k.startswith("vision_model.") else "vision_model." + k
+
+
+def load_siglip(model_dir):
+    """A transformers SiglipModel or SiglipVisionModel directory (google/siglip-so400m-patch14-384; adv_grpo/rewards.py:69-144) ->
+    (vision state dict with ``vision_model.`` keys, SiglipVisionConfig)."""
+    cfg = read_config(model_dir)
+    _class(cfg, model_dir, "SiglipModel", "SiglipVisionModel")
+    v = (cfg.get("vision_config") or {}) if (cfg.get("_class_name") or (cfg.get("architectures") or [None])[0]) == "SiglipModel" else cfg
+    get = lambda k: v[k] if v.get(k) is not None else _SIGLIP_VISION_DEFAULTS[k]
+    unsupported = []
+    if v.get("vision_use_head", True) is False:
+        unsupported.append("vision_use_head = false (the reward pools with the attention-pooling head)")
+    if get("hidden_act") != "gelu_pytorch_tanh":
+        unsupported.append(f"hidden_act = {get('hidden_act')!r} (only 'gelu_pytorch_tanh' is implemented)")
+    if int(get("patch_size")) != 14:
+        unsupported.append(f"patch_size = {get('patch_size')} (the preprocessing kernel writes 14 x 14 patch rows)")
+    if int(get("num_channels")) != 3:
+        unsupported.append(f"num_channels = {get('num_channels')} (RGB only)")
+    D, H = int(get("hidden_size")), int(get("num_attention_heads"))
+    if D % H or D // H not in (64, 72, 80):
+        unsupported.append(f"head dim {D}/{H} (the attention kernels of this path serve 64, 72 and 80)")
+    if unsupported:
+        raise HubError(f"{model_dir}: not implemented: " + "; ".join(unsupported))
+    out = SiglipVisionConfig(hidden=D, layers=int(get("num_hidden_layers")), heads=H, mlp=int(get("intermediate_size")),
+                             image_size=int(get("image_size")), patch=14, eps=float(get("layer_norm_eps")))
+    want = synthetic.shapes(synthetic.siglip_weights, out)
+    have = {}
+    for k, shape in header_shapes(model_dir).items():
+        n = _siglip_rename(k)
+        if n is not None:
+            have[n] = shape
+    validate(have, want, model_dir, optional={"vision_model.embeddings.position_ids"})
+    return read_tensors(model_dir, keys=set(want), rename=_siglip_rename), out
 
 
 # ---------------------------------------------------------------------------------------------------------------- Qwen-Image

@@ -90,6 +90,26 @@ class DinoConfig:  # timm vit_base_patch14_dinov2.lvd142m
 
 
 @dataclass
+class SiglipVisionConfig:  # google/siglip-so400m-patch14-384 vision tower (transformers SiglipVisionConfig; siglip_image_similarity)
+    hidden: int = 1152
+    layers: int = 27
+    heads: int = 16
+    mlp: int = 4304
+    image_size: int = 384
+    patch: int = 14
+    eps: float = 1e-6
+    act: str = "gelu_tanh"      # transformers' "gelu_pytorch_tanh"
+
+    @property
+    def head_dim(self):
+        return self.hidden // self.heads
+
+    @property
+    def tokens(self):
+        return (self.image_size // self.patch) ** 2
+
+
+@dataclass
 class QwenMMDiTConfig:  # Qwen/Qwen-Image transformer (diffusers QwenImageTransformer2DModel; BASELINE config 5)
     num_layers: int = 60
     num_heads: int = 24

@@ -108,3 +108,19 @@ def dino_patches(images, size=518, x3=False):
                                                    patches.data_ptr(), B, H, W, size, size, _f3(IMAGENET_MEAN),
                                                    _f3(IMAGENET_STD), _lib.stream_ptr()))
     return patches
+
+
+def siglip_patches(images, size=384):
+    """siglip_image_similarity's preprocessing (adv_grpo/rewards.py:87-115): images [B,3,H,W] f32 / bf16 (in [0,1]) or uint8 (divided by
+    255 in f32 on the device), device -> bf16 [B*(size//14)^2, 640] patch rows.  Bicubic resize to size x size in the input's dtype, then
+    (x - 0.5) / 0.5 in f32, then bf16 (a bf16 input's resize result is rounded to bf16 first, as F.interpolate returns it)."""
+    lib = _lib.load()
+    B, C, H, W = images.shape
+    assert C == 3
+    P = (size // 14) ** 2
+    patches = torch.empty(B * P, 640, dtype=torch.bfloat16, device=images.device)
+    images = images.contiguous()
+    dt = _lib.U8 if images.dtype == torch.uint8 else _lib.dtype_code(images.dtype)
+    _lib.check(lib.advgrpo_siglip_preprocess_patches(_lib.ptr(images), dt, patches.data_ptr(), B, H, W, size,
+                                                     _lib.stream_ptr()))
+    return patches

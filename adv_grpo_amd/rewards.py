@@ -4,7 +4,8 @@ Mirror of adv_grpo/rewards.py:1012-1095: ``multi_score(device, {name: weight}) -
 metadata, scorer=None, ref_images=None, only_strict=True, head=None, ...) -> ({name: scores, ..., 'avg':
 [...]}, {})`` with the same name-dispatched calling conventions (factory takes ``device`` iff it has a
 parameter of that name; co-train scorers receive the backbone / head as arguments).  Registered: the six
-scorers on the hot path and ``jpeg_compressibility`` (on-device JPEG, jpeg.py); the remote-server /
+scorers on the hot path, ``jpeg_compressibility`` (on-device JPEG, jpeg.py) and the SigLIP eval reward
+``siglip_image_similarity`` (vit.SiglipVision); the remote-server /
 VLM scorers are out of scope and raise a clear error.  New scorers can be added with ``register_scorer``.
 """
 import inspect
@@ -15,7 +16,7 @@ from . import vit
 
 _OUT_OF_SCOPE = ("deqa", "video_ocr", "imagereward", "qwenvl", "aesthetic", "unifiedreward",
                  "geneval", "clipscore", "image_similarity_eval", "constractive_external", "discriminator",
-                 "pickscore_patch", "dino_multi_cotrain", "siglip_cotrain", "siglip_image_similarity")
+                 "pickscore_patch", "dino_multi_cotrain", "siglip_cotrain")
 # scorers a shipped experiment of config/grpo.py names although they are outside SURVEY.md 8's six: why, per name
 _WHY_NOT = {
     "dino_multi_cotrain": "the multi-layer DINOv2 fusion scorer (adv_grpo/rewards.py:1032, config/grpo.py `dino_cotrain_sd3_multi_fast`, tune_layer = (11,), "
@@ -133,6 +134,52 @@ def configure_dino(model):
     _DINO["model"] = model
 
 
+def siglip_image_similarity_score(device):
+    """rewards.py:69-144 (eval): max over the reference images of the cosine similarity of SigLIP so400m/14 pooled embeddings.
+    On the kernels of the path: the fused preprocess (bicubic 384 + (x - 0.5) / 0.5 with the reference's bf16 rounding points),
+    the bf16 tower and attention-pooling head (vit.SiglipVision), rows L2-normalised by ``gather_l2norm_rows``, the [N, M] similarity
+    matrix by the MFMA GEMM with f32 output (the reference rounds it to bf16: DESIGN.md section 3); only the row maximum is index
+    plumbing.  Needs a backbone: configure with rewards.configure_siglip(model)."""
+    def _rows(model, images):
+        from . import _lib
+        lib = _lib.load()
+        if not isinstance(images, torch.Tensor):                                # RW:91-92
+            images = torch.tensor(images, dtype=torch.float32)
+        if images.shape[-1] == 3:                                               # NHWC -> NCHW (RW:99-100)
+            images = images.permute(0, 3, 1, 2)
+        images = images.to(device)
+        if images.dtype in (torch.float16, torch.float64):                      # the kernel resizes f32 / bf16 / u8 (DESIGN.md section 3)
+            images = images.float()
+        elif images.dtype not in (torch.float32, torch.bfloat16, torch.uint8):
+            raise TypeError(f"siglip_image_similarity: images must be floating point or uint8, not {images.dtype}")
+        if images.dtype != torch.uint8 and images.max() > 1.0:                  # RW:95-96 (uint8: divided by 255 in the kernel)
+            images = images / 255.0
+        emb = model.pooler_output(images=images)                                # [N, D] bf16
+        N, Dm = emb.shape
+        rows = torch.empty(N, Dm, dtype=torch.bfloat16, device=emb.device)
+        _lib.check(lib.advgrpo_gather_l2norm_rows(emb.data_ptr(), None, rows.data_ptr(), N, 1, Dm, 0, 0.0, _lib.stream_ptr()))
+        return rows
+
+    def _fn(images, ref_images):
+        from . import ops
+        if ref_images is None:
+            raise ValueError("siglip_image_similarity: needs ref_images (the prompt's reference images); training-time scoring passes none")
+        model = _SIGLIP.get("model")
+        if model is None:
+            raise RuntimeError("siglip_image_similarity: call rewards.configure_siglip(model) first (no checkpoint download)")
+        scores = ops.gemm(_rows(model, images), _rows(model, ref_images), out_dtype=torch.float32)    # [N, M] (RW:136)
+        return scores.max(dim=1).values, {"pairwise": scores}
+    return _fn
+
+
+_SIGLIP = {}
+
+
+def configure_siglip(model):
+    """Backbone of ``siglip_image_similarity``: a vit.SiglipVision (e.g. from hub.load_siglip or synthetic.siglip_weights)."""
+    _SIGLIP["model"] = model
+
+
 _OCR = {}
 
 
@@ -185,6 +232,7 @@ score_functions = {
     "dino_cotrain": dino_cotrain_score,
     "dino_patch_cotrain": dino_patch_cotrain_score,
     "jpeg_compressibility": jpeg_compressibility,
+    "siglip_image_similarity": siglip_image_similarity_score,
 }
 
 
@@ -209,7 +257,7 @@ def multi_score(device, score_dict):
         total = []
         details = {}
         for name, weight in score_dict.items():
-            if name == "image_similarity":
+            if name in ("image_similarity", "siglip_image_similarity"):
                 scores, _ = score_fns[name](images, ref_images)
             elif name == "pickscore_cotrain":
                 scores, _ = score_fns[name](scorer, images, prompts, metadata)

@@ -357,6 +357,33 @@ def dino_weights(cfg, seed=888):
     return W
 
 
+def siglip_weights(cfg, seed=1111):
+    """fp32 weights keyed like transformers SiglipVisionModel.state_dict() (prefix ``vision_model.``; a SiglipModel checkpoint holds the
+    same keys beside its text_model.*): patch conv + position table, pre-LN encoder layers, post_layernorm, attention-pooling head."""
+    g = _gen(seed)
+    D, v = cfg.hidden, "vision_model"
+    W = {f"{v}.embeddings.patch_embedding.weight": _randn(D, 3, cfg.patch, cfg.patch, generator=g) / math.sqrt(3 * cfg.patch ** 2),
+         f"{v}.embeddings.patch_embedding.bias": _randn(D, generator=g) * 0.1,
+         f"{v}.embeddings.position_embedding.weight": _randn(cfg.tokens, D, generator=g) * 0.5}
+    for i in range(cfg.layers):
+        p = f"{v}.encoder.layers.{i}"
+        _ln(W, f"{p}.layer_norm1", D, g); _ln(W, f"{p}.layer_norm2", D, g)
+        for nm in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            linear_(W, f"{p}.self_attn.{nm}", D, D, g)
+        linear_(W, f"{p}.mlp.fc1", cfg.mlp, D, g)
+        linear_(W, f"{p}.mlp.fc2", D, cfg.mlp, g)
+    _ln(W, f"{v}.post_layernorm", D, g)
+    h = f"{v}.head"
+    W[f"{h}.probe"] = _randn(1, 1, D, generator=g)
+    W[f"{h}.attention.in_proj_weight"] = _randn(3 * D, D, generator=g) / math.sqrt(D)
+    W[f"{h}.attention.in_proj_bias"] = _randn(3 * D, generator=g) * 0.1
+    linear_(W, f"{h}.attention.out_proj", D, D, g)
+    _ln(W, f"{h}.layernorm", D, g)
+    linear_(W, f"{h}.mlp.fc1", cfg.mlp, D, g)
+    linear_(W, f"{h}.mlp.fc2", D, cfg.mlp, g)
+    return W
+
+
 def dino_head_weights(in_dim=768, hidden=512, seed=999):
     """DINOHead (train_sd3_fast_dino_patch.py:592-603): layers.0 Linear(in,512), layers.2 Linear(512,1)."""
     g = _gen(seed)

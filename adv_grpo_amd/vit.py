@@ -1,8 +1,9 @@
-"""ViT reward towers on the gfx950 kernels: CLIP ViT-H/14 (PickScore_v1) and DINOv2 ViT-B/14.
+"""ViT reward towers on the gfx950 kernels: CLIP ViT-H/14 (PickScore_v1), DINOv2 ViT-B/14 and SigLIP so400m/14.
 
 Stand in for transformers' ``CLIPModel.get_image_features / get_text_features``
 (adv_grpo/pickscore_scorer.py:40-44) and timm's ``forward_features`` (adv_grpo/rewards.py:397,
-scripts/train_sd3_fast_dino_patch.py:183-184).  One encoder-layer routine serves all three towers:
+scripts/train_sd3_fast_dino_patch.py:183-184), and transformers' ``SiglipVisionModel.pooler_output`` (adv_grpo/rewards.py:69-144).
+One encoder-layer routine serves all four towers:
 LayerNorm (row kernel) -> packed QKV GEMM -> fused attention reading q|k|v in place -> out-proj GEMM with
 the residual (and DINOv2's LayerScale as the gate operand) in its epilogue -> LayerNorm -> MLP GEMMs with
 GELU / residual epilogues.
@@ -211,6 +212,88 @@ class DinoV2:
         x.view(B, S, D)[:, 0] = self.cls
         x = self.enc(x, B, S)
         return ops.layernorm_mod(x, w=self.norm[0], b=self.norm[1], eps=1e-6).view(B, S, D)
+
+
+def _pad_rows(t, n, dev):
+    """Zero rows appended up to n (a weight [rows, K] or a bias [rows])."""
+    out = torch.zeros((n,) + tuple(t.shape[1:]), dtype=torch.float32, device=t.device)
+    out[:t.shape[0]] = t
+    return _bf(out, dev)
+
+
+def _pad_cols(t, n, dev):
+    out = torch.zeros(t.shape[0], n, dtype=torch.float32, device=t.device)
+    out[:, :t.shape[1]] = t
+    return _bf(out, dev)
+
+
+class SiglipVision:
+    """transformers SiglipVisionModel (google/siglip-so400m-patch14-384) in bf16 with its state_dict names (``vision_model.`` prefix):
+    patch conv + position rows (no CLS token), 27 pre-LN layers (head dim 72), post_layernorm over every token, then the attention-
+    pooling head -- h = MHA(probe, x, x) (no residual around it), h = h + mlp(layernorm(h)) -- whose output is ``pooler_output``.
+
+    The MLP width 4304 is not a multiple of the GEMM's K granule (64): fc1's output rows / bias and fc2's input columns are zero-padded to
+    4352; gelu_tanh(0) = 0, so the padding adds exact zeros.  The probe's q row (probe Wq^T + bq) does not depend on the image: computed
+    once here; per image the head runs a K|V GEMM over the 729 rows, the head-dim-72 attention with one query (q batch stride 0),
+    out-proj, LayerNorm and the MLP GEMMs at M = B."""
+
+    def __init__(self, sd, cfg, device="cuda"):
+        self.cfg, dev = cfg, torch.device(device)
+        self.device = dev
+        v, D = "vision_model", cfg.hidden
+        self.mlp_pad = F = (cfg.mlp + 63) // 64 * 64
+        layers = pack_clip_layers(sd, v, cfg.layers, dev)
+        for L in layers:
+            L["fc1.w"], L["fc1.b"], L["fc2.w"] = _pad_rows(L["fc1.w"], F, dev), _pad_rows(L["fc1.b"], F, dev), _pad_cols(L["fc2.w"], F, dev)
+        self.enc = _Encoder(layers, cfg.heads, cfg.eps, cfg.act)
+        self.patch_w = _pad_patch_weight(sd[f"{v}.embeddings.patch_embedding.weight"], dev)
+        self.patch_b = _bf(sd[f"{v}.embeddings.patch_embedding.bias"], dev)
+        self.pos = _bf(sd[f"{v}.embeddings.position_embedding.weight"], dev)
+        self.post_ln = (_bf(sd[f"{v}.post_layernorm.weight"], dev), _bf(sd[f"{v}.post_layernorm.bias"], dev))
+        h = f"{v}.head"
+        in_w, in_b = sd[f"{h}.attention.in_proj_weight"], sd[f"{h}.attention.in_proj_bias"]
+        self.kv_w, self.kv_b = _bf(in_w[D:], dev), _bf(in_b[D:], dev)
+        self.q = ops.gemm(_bf(sd[f"{h}.probe"].reshape(1, D), dev), _bf(in_w[:D], dev), bias=_bf(in_b[:D], dev))     # [1, D]
+        self.out_w, self.out_b = _bf(sd[f"{h}.attention.out_proj.weight"], dev), _bf(sd[f"{h}.attention.out_proj.bias"], dev)
+        self.head_ln = (_bf(sd[f"{h}.layernorm.weight"], dev), _bf(sd[f"{h}.layernorm.bias"], dev))
+        self.head_fc1 = (_pad_rows(sd[f"{h}.mlp.fc1.weight"], F, dev), _pad_rows(sd[f"{h}.mlp.fc1.bias"], F, dev))
+        self.head_fc2 = (_pad_cols(sd[f"{h}.mlp.fc2.weight"], F, dev), _bf(sd[f"{h}.mlp.fc2.bias"], dev))
+        self._pos_cache = {}
+
+    def eval(self):
+        return self
+
+    @torch.no_grad()
+    def last_hidden_state(self, pixel_patches):
+        """patch rows [B*P, 640] (preprocess.siglip_patches) -> post_layernorm(encoder(embeddings)) [B*P, D] bf16."""
+        cfg = self.cfg
+        P, D = cfg.tokens, cfg.hidden
+        B = pixel_patches.shape[0] // P
+        ops.cached(self._pos_cache, B, lambda: self.pos.repeat(B, 1).contiguous())
+        x = torch.empty(B * P, D, dtype=torch.bfloat16, device=pixel_patches.device)
+        ops.gemm(pixel_patches, self.patch_w, bias=self.patch_b, out=x, residual=self._pos_cache[B])
+        x = self.enc(x, B, P)
+        return ops.layernorm_mod(x, w=self.post_ln[0], b=self.post_ln[1], eps=cfg.eps)
+
+    @torch.no_grad()
+    def pool(self, x, B):
+        """The attention-pooling head: last_hidden_state [B*P, D] -> pooler_output [B, D] bf16."""
+        cfg = self.cfg
+        P, D = cfg.tokens, cfg.hidden
+        kv = ops.gemm(x, self.kv_w, bias=self.kv_b).view(B, P, 2 * D)
+        o = ops.attention(self.q.view(1, 1, D).expand(B, 1, D), kv[:, :, :D], kv[:, :, D:], cfg.heads)
+        h = ops.gemm(o.view(B, D), self.out_w, bias=self.out_b)
+        n = ops.layernorm_mod(h, w=self.head_ln[0], b=self.head_ln[1], eps=cfg.eps)
+        m = ops.gemm(n, self.head_fc1[0], bias=self.head_fc1[1], act=cfg.act)
+        return ops.gemm(m, self.head_fc2[0], bias=self.head_fc2[1], residual=h, out=h)
+
+    @torch.no_grad()
+    def pooler_output(self, images=None, pixel_patches=None):
+        """images: [B,3,H,W] on the device, f32 / bf16 in [0,1] or uint8; the reference's bicubic-384 + (x - 0.5) / 0.5 is fused in."""
+        if pixel_patches is None:
+            pixel_patches = preprocess.siglip_patches(images, self.cfg.image_size)
+        B = pixel_patches.shape[0] // self.cfg.tokens
+        return self.pool(self.last_hidden_state(pixel_patches), B)
 
 
 class DinoHead:

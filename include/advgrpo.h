@@ -214,7 +214,7 @@ int advgrpo_unpatchify(const void* tokens, void* out, int out_dtype, int B, int 
  * (sd3_pipeline_with_logprob_fast.py:630-637; adv_grpo/rewards.py:397; pickscore_scorer.py:40-44).
  * q/k/v/o are [B, S, H*head_dim]-shaped VIEWS: element (b, s, h, d) at
  * ptr + b*bs + s*ld + h*head_dim + d, so packed QKV GEMM outputs are consumed in place.
- * head_dim: 64, 80 or 128 (128: the Qwen-Image MMDiT; non-causal, 16-byte aligned output rows).  ld{q,k,v} % 8 == 0, ldo % 4 == 0.
+ * head_dim: 64, 72, 80 or 128 (72: SigLIP, exactly 72 columns per head stored; 128: the Qwen-Image MMDiT; non-causal, 16-byte aligned output rows).  ld{q,k,v} % 8 == 0, ldo % 4 == 0.
  * lse (optional, f32 [B,H,Sq]): base-2 log-sum-exp of the scaled scores, consumed by the backward. */
 int advgrpo_attention_fwd(const void* q, const void* k, const void* v, void* o,
                           int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
@@ -523,8 +523,8 @@ int advgrpo_vae_decode(const advgrpo_vae_decoder_desc* decoder, const void* late
  * 24 causal layers, 16 x 64) and timm's vit_base_patch14_dinov2 blocks with LayerScale behind forward_features (adv_grpo/rewards.py:397,
  * scripts/train_sd3_fast_dino_patch.py:183-184; 12 layers, 12 x 64).  Per layer: x += [ls1 *] attn(LN(x)); x += [ls2 *] fc2(act(fc1(LN(x)))),
  * q | k | v stacked along N in qkv_w / qkv_b, weights in nn.Linear layout [N, K], all bf16; x [B S, D] token rows, updated in place;
- * `layers` is a HOST array (device pointers inside).  act: the GEMM activation codes (2 GELU-erf, 4 quick-GELU); head dim D / H must be 64
- * or 80.  The embedding in front and the final norm / projection behind stay with the caller.  Bit-identical to the same launches issued one
+ * `layers` is a HOST array (device pointers inside).  act: the GEMM activation codes (1 GELU-tanh, 2 GELU-erf, 4 quick-GELU); head dim D / H
+ * must be 64, 72 (SigLIP so400m/14, 27 layers of 16 x 72) or 80.  The embedding in front and the final norm / projection behind stay with the caller.  Bit-identical to the same launches issued one
  * by one (adv_grpo_amd/vit.py keeps that sequencing as the check). */
 typedef struct advgrpo_vit_layer {
     const void *ln1_w, *ln1_b, *qkv_w, *qkv_b, *out_w, *out_b, *ls1;      /* ls1 / ls2: LayerScale gamma [D] or NULL */
@@ -722,6 +722,15 @@ int64_t advgrpo_jpeg_workspace_bytes(int N, int H, int W);
 int64_t advgrpo_jpeg_max_file_bytes(int H, int W);
 int advgrpo_jpeg_encode(const void* images, int dtype, int layout, int N, int H, int W, int quality, int64_t* sizes,
                         uint8_t* files, int64_t file_stride, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ SigLIP (siglip_image_similarity reward)
+ * Preprocessing of siglip_image_similarity_score (adv_grpo/rewards.py:87-115): F.interpolate(bicubic, A = -0.75,
+ * align_corners=False) to OS x OS in the input's dtype, (x - 0.5) / 0.5 in f32, bf16.  image [B,3,H,W] F32 / BF16 / U8 (U8:
+ * x * (1/255) in f32 first); a bf16 input's resize result is rounded to bf16 before the normalisation, an f32 one is not.
+ * patches: bf16 [B*P, 640] im2col rows of the 14/14 patch conv (588 real columns + zeros), P = (OS/14)^2; pixels past
+ * (OS/14)*14 are never read by the conv and are not computed.  The SigLIP tower runs on advgrpo_vit_forward (head dim 72) and
+ * advgrpo_attention_fwd (head dim 72; its attention-pooling head passes Sq = 1 and a q batch stride of 0). */
+int advgrpo_siglip_preprocess_patches(const void* image, int image_dtype, void* patches, int B, int H, int W, int OS, void* stream);
 
 #ifdef __cplusplus
 }

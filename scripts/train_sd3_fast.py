@@ -83,6 +83,9 @@ def main():
     for rname in list(cfg.reward_fn.keys()):
         if rname in _rw._OUT_OF_SCOPE:
             raise SystemExit(f"{args.config}: reward '{rname}': " + _rw._WHY_NOT.get(rname, "outside the accelerated hot path (SURVEY.md 2.1 row 5)"))
+        if rname == "siglip_image_similarity":
+            raise SystemExit(f"{args.config}: reward '{rname}' compares every image with the prompt's reference images, and training-time "
+                             "scoring passes none (neither does the reference, TD:901): it is an eval reward (Trainer.evaluate)")
         if rname not in _rw.score_functions:
             raise SystemExit(f"{args.config}: unknown reward '{rname}' (registered: {', '.join(sorted(_rw.score_functions))})")
     torch.cuda.set_device(local)
