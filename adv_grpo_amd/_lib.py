@@ -231,6 +231,8 @@ SIGNATURES = {
     "advgrpo_jpeg_max_file_bytes": (c_int64, [c_int, c_int]),
     "advgrpo_jpeg_encode": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, c_int64, _P]),
     "advgrpo_siglip_preprocess_patches": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, _P]),
+    "advgrpo_tv_resize_patches": (c_int, [_P, c_int, _P] + [c_int] * 9 + [POINTER(c_float), POINTER(c_float), _P]),
+    "advgrpo_aesthetic_head": (c_int, [_P, c_int, c_int] + [_P] * 10 + [_P, _P]),
 }
 
 

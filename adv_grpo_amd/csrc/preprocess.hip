@@ -12,8 +12,10 @@
 //   * DINO path: torch's upsample_bicubic2d (A = -0.75, align_corners=False, no antialias) in f32 on
 //     bf16 inputs, rounded to bf16, then (x - mean)/std in f32, rounded to bf16.
 //   * SigLIP path: the same resize in the input's own dtype (no bf16 rounding of f32 / u8 inputs), (x - 0.5)/0.5 in f32, bf16.
+//   * clipscore path: torchvision's tensor Resize (bilinear, antialias) + CenterCrop + Normalize, mirroring torch's GPU kernel.
 //   * reward epilogues: gather + L2-normalise the CLS / sampled patch tokens, head second layer +
-//     0.7/0.3 mix (rewards.py:399-421); PickScore exp(logit_scale) * cos / 26 (pickscore_scorer.py:40-52).
+//     0.7/0.3 mix (rewards.py:399-421); PickScore exp(logit_scale) * cos / 26 (pickscore_scorer.py:40-52); the
+//     aesthetic MLP head (aesthetic_scorer.py).
 #include "common.hpp"
 
 namespace advgrpo {
@@ -231,6 +233,169 @@ __global__ __launch_bounds__(64) void pickscore_pairs_kernel(const bf16_t* __res
     if (lane == 0) out[b] = logit_scale_exp * it / (sqrtf(ii) * sqrtf(tt)) / 26.0f;
 }
 
+// ---- torchvision T.Resize(shortest edge, bilinear, antialias) + T.CenterCrop + T.Normalize on a tensor (ClipScorer,
+// adv_grpo/clip_scorer.py), computed only inside the crop window.  Mirrors torch's GPU upsample_bilinear2d_aa (UpSampleBilinear2d.cu
+// upsample_gen2d_aa_out_frame + UpSample.cuh upsample_antialias::*) at scalar_t = accscalar_t = float: torchvision casts an input that
+// is not f32 / f64 to f32 before F.interpolate and back after it.  Per output pixel: the x and y spans and weights in f32
+// (center = scale (i + 0.5), xmin = max(int(center - support + 0.5), 0), triangle taps at (j + xmin - center + 0.5) / max(scale, 1),
+// each divided by their f32 sum), the horizontal pass over the ysize input rows, then the vertical pass over those row results.
+// Contraction is off in this code (`#pragma clang fp contract(off)`; fusing 1 - x * invscale in the filter moved 0.3 % of the outputs):
+// the only fused multiply-adds are the explicit ones, one per tap after the first, which is how torch's build contracts
+// `output += t * wts` (checked against torch's GPU kernel).
+struct AaSpan {
+    int xmin, xsize;
+    float xmc, invscale, total;     // xmin - center, 1 / max(scale, 1), sum of the unnormalised taps
+};
+
+__device__ inline float aa_filter(float x) {
+#pragma clang fp contract(off)
+    if (x < 0.f) x = -x;
+    return x < 1.f ? 1.f - x : 0.f;
+}
+
+__device__ inline float aa_tap(const AaSpan& a, int j) {
+#pragma clang fp contract(off)
+    return aa_filter(((float)j + a.xmc + 0.5f) * a.invscale);
+}
+
+__device__ inline AaSpan aa_span(int i, int in_size, float scale) {
+#pragma clang fp contract(off)
+    AaSpan a;
+    const float support = scale >= 1.f ? scale : 1.f;                        // (interp_size / 2) * scale, interp_size = 2
+    const float center = scale * ((float)i + 0.5f);         // scale * (i + 0.5): exact in double, rounded once
+    // f32 (center -/+ support), then + 0.5 in double (a double literal in torch), truncated toward zero
+    a.xmin = max((int)((double)(center - support) + 0.5), 0);
+    a.xsize = min((int)((double)(center + support) + 0.5), in_size) - a.xmin;
+    a.xmc = (float)a.xmin - center;
+    a.invscale = scale >= 1.f ? 1.f / scale : 1.f;
+    a.total = 0.f;
+    for (int j = 0; j < a.xsize; ++j) a.total += aa_tap(a, j);
+    return a;
+}
+
+__device__ inline float aa_weight(const AaSpan& a, int j) {
+#pragma clang fp contract(off)
+    const float w = aa_tap(a, j);
+    return a.total != 0.f ? w / a.total : w;
+}
+
+__device__ inline float ld_img_tv(const void* img, int dt, int64_t i) {
+#pragma clang fp contract(off)
+    if (dt == ADVGRPO_U8) return (float)reinterpret_cast<const uint8_t*>(img)[i] / 255.0f;   // torch.tensor(u8) / 255.0
+    return ld_img(img, dt, i);
+}
+
+// img [B,3,H,W] (F32 / BF16 / U8) resized to scale (H / RH, W / RW); the OS x OS window at (top, left) of the resized image is
+// normalised and written as 14x14 patch rows.  bf16_ops (a bf16 input): the resize result, x - mean and the division are each rounded
+// to bf16 (torch's bf16 elementwise ops), and mean / std arrive as bf16 values.
+template <bool X3>
+__global__ void tv_resize_patches_kernel(const void* __restrict__ img, int dt, bf16_t* __restrict__ patches, int B, int H, int W,
+                                         float scale_h, float scale_w, int top, int left, int OS, float3 mean, float3 stdv,
+                                         int bf16_ops) {
+#pragma clang fp contract(off)
+    const int gw = OS / PATCH;
+    const int P = gw * gw;
+    const int64_t total = (int64_t)B * P * PATCH_KPAD;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int col = i % PATCH_KPAD;
+        const int64_t prow = i / PATCH_KPAD;
+        bf16_t* o3 = patches + prow * (3 * PATCH_KPAD) + col;
+        if (col >= PATCH_K) {
+            if (X3) { o3[0] = 0; o3[PATCH_KPAD] = 0; o3[2 * PATCH_KPAD] = 0; }
+            else patches[i] = 0;
+            continue;
+        }
+        const int p = prow % P, b = prow / P;
+        const int c = col / (PATCH * PATCH), iy = (col / PATCH) % PATCH, ix = col % PATCH;
+        const int ry = top + (p / gw) * PATCH + iy, rx = left + (p % gw) * PATCH + ix;      // pixel of the resized image
+        const AaSpan sx = aa_span(rx, W, scale_w), sy = aa_span(ry, H, scale_h);
+        const int64_t base = (int64_t)(b * 3 + c) * H * W;
+        float out = 0.f;
+        for (int y = 0; y < sy.xsize; ++y) {
+            const int64_t row = base + (int64_t)(sy.xmin + y) * W + sx.xmin;
+            float h = ld_img_tv(img, dt, row) * aa_weight(sx, 0);
+            for (int x = 1; x < sx.xsize; ++x) h = __fmaf_rn(ld_img_tv(img, dt, row + x), aa_weight(sx, x), h);
+            const float wy = aa_weight(sy, y);
+            out = y == 0 ? h * wy : __fmaf_rn(h, wy, out);
+        }
+        const float m = c == 0 ? mean.x : (c == 1 ? mean.y : mean.z);
+        const float s = c == 0 ? stdv.x : (c == 1 ? stdv.y : stdv.z);
+        float v;
+        if (bf16_ops) v = round_bf16(round_bf16(round_bf16(out) - m) / s);
+        else v = (out - m) / s;
+        if (X3) {
+            const bf16_t hi = f2bf(v);
+            o3[0] = hi; o3[PATCH_KPAD] = hi; o3[2 * PATCH_KPAD] = f2bf(v - bf2f(hi));
+        } else {
+            patches[i] = f2bf(v);
+        }
+    }
+}
+
+// ---- LAION aesthetic predictor (adv_grpo/aesthetic_scorer.py): e / ||e|| -> Linear 768-1024-128-64-16-1 (no activations; dropout is
+// inactive in eval).  One workgroup of 4 waves scores AES_ROWS rows; every value is f32.  Each output of a layer is one wave's dot
+// product: lane l runs a fused multiply-add chain over k = l, l + 64, ... in increasing k, the 64 partial sums meet in the fixed DPP
+// tree of wave_sum, and the bias is added last.  The squared norm is summed the same way.  A row's score therefore takes the same
+// operations in the same order whatever the batch size and wherever the row sits in it.  No atomics.
+constexpr int AES_D = 768, AES_ROWS = 4, AES_PITCH = 1024;      // input width, rows per workgroup, LDS row pitch (the widest layer)
+
+struct AesWeights { const float* w[5]; const float* b[5]; };
+
+// y[r, o] = sum_k w[o, k] x[r, k] + bias[o] for the AES_ROWS rows of the workgroup, one wave per output o
+__device__ inline void aes_dense(const float* __restrict__ w, const float* __restrict__ bias, const float* xin, int K, float* yout, int N) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int o = wave; o < N; o += 4) {
+        const float* wr = w + (int64_t)o * K;
+        float acc[AES_ROWS];
+#pragma unroll
+        for (int r = 0; r < AES_ROWS; ++r) acc[r] = 0.f;
+        for (int k = lane; k < K; k += 64) {
+            const float wk = wr[k];
+#pragma unroll
+            for (int r = 0; r < AES_ROWS; ++r) acc[r] = __fmaf_rn(wk, xin[r * AES_PITCH + k], acc[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < AES_ROWS; ++r) {
+            const float t = wave_sum(acc[r]);
+            if (lane == 0) yout[r * AES_PITCH + o] = t + bias[o];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void aesthetic_head_kernel(const void* __restrict__ emb, int dt, int N, AesWeights wt,
+                                                             float* __restrict__ scores) {
+#pragma clang fp contract(off)
+    __shared__ float bufA[AES_ROWS * AES_PITCH], bufB[AES_ROWS * AES_PITCH];
+    const int row0 = blockIdx.x * AES_ROWS;
+    const int rows = min(AES_ROWS, N - row0);               // rows past N are zeros, normalised to zeros, and never stored
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int idx = threadIdx.x; idx < AES_ROWS * AES_D; idx += blockDim.x) {
+        const int r = idx / AES_D, k = idx % AES_D;
+        bufB[r * AES_PITCH + k] = r < rows ? ld_img(emb, dt, (int64_t)(row0 + r) * AES_D + k) : 0.f;
+    }
+    __syncthreads();
+    {                                                        // embed / torch.linalg.vector_norm(embed, dim=-1, keepdim=True): wave r, row r
+        const float* e = bufB + wave * AES_PITCH;
+        float sq = 0.f;
+        for (int k = lane; k < AES_D; k += 64) sq = __fmaf_rn(e[k], e[k], sq);
+        const float nrm = __fsqrt_rn(wave_sum(sq));
+        for (int k = lane; k < AES_D; k += 64) bufA[wave * AES_PITCH + k] = wave < rows ? e[k] / nrm : 0.f;
+    }
+    __syncthreads();
+    aes_dense(wt.w[0], wt.b[0], bufA, 768, bufB, 1024);
+    __syncthreads();
+    aes_dense(wt.w[1], wt.b[1], bufB, 1024, bufA, 128);
+    __syncthreads();
+    aes_dense(wt.w[2], wt.b[2], bufA, 128, bufB, 64);
+    __syncthreads();
+    aes_dense(wt.w[3], wt.b[3], bufB, 64, bufA, 16);
+    __syncthreads();
+    aes_dense(wt.w[4], wt.b[4], bufA, 16, bufB, 1);
+    __syncthreads();
+    if (threadIdx.x < rows) scores[row0 + threadIdx.x] = bufB[threadIdx.x * AES_PITCH];
+}
+
 }  // namespace advgrpo
 
 using namespace advgrpo;
@@ -315,6 +480,44 @@ extern "C" int advgrpo_siglip_preprocess_patches(const void* image, int image_dt
                   "siglip_preprocess: image dtype must be f32, bf16 or u8");
     hipLaunchKernelGGL(bicubic_patches_kernel<PRE_SIGLIP>, dim3(4096), dim3(256), 0, as_stream(stream), image, image_dtype,
                        (bf16_t*)patches, B, H, W, OS, OS, make_float3(0.5f, 0.5f, 0.5f), make_float3(0.5f, 0.5f, 0.5f));
+    ADVGRPO_LAUNCH_CHECK();
+    return 0;
+}
+
+/* clipscore's torchvision preprocessing (see the kernel): image [B,3,H,W] f32 / bf16 / u8 resized to RH x RW, the OS x OS window at
+   (top, left) normalised and written as patch rows: bf16 [B*P, 640], or with x3 the split-bf16 [B*P, 3*640]; P = (OS/14)^2 */
+extern "C" int advgrpo_tv_resize_patches(const void* image, int image_dtype, void* patches, int x3, int B, int H, int W, int RH, int RW,
+                                         int top, int left, int OS, const float* mean3_host, const float* std3_host, void* stream) {
+    ADVGRPO_CHECK(image && patches && mean3_host && std3_host, "tv_resize_patches: null pointer");
+    ADVGRPO_CHECK(B > 0 && H > 0 && W > 0 && RH > 0 && RW > 0 && OS >= PATCH && OS % PATCH == 0,
+                  "tv_resize_patches: bad shape (B=%d H=%d W=%d RH=%d RW=%d OS=%d)", B, H, W, RH, RW, OS);
+    ADVGRPO_CHECK(top >= 0 && left >= 0 && top + OS <= RH && left + OS <= RW,
+                  "tv_resize_patches: the %d x %d crop at (%d, %d) leaves the %d x %d resized image", OS, OS, top, left, RH, RW);
+    ADVGRPO_CHECK(image_dtype == ADVGRPO_F32 || image_dtype == ADVGRPO_BF16 || image_dtype == ADVGRPO_U8,
+                  "tv_resize_patches: image dtype must be f32, bf16 or u8");
+    const float sh = (float)H / (float)RH, sw = (float)W / (float)RW;      // area_pixel_compute_scale<float>, align_corners = False
+    const float3 m = make_float3(mean3_host[0], mean3_host[1], mean3_host[2]);
+    const float3 sd = make_float3(std3_host[0], std3_host[1], std3_host[2]);
+    const int bf16_ops = image_dtype == ADVGRPO_BF16;
+    if (x3)
+        hipLaunchKernelGGL(tv_resize_patches_kernel<true>, dim3(4096), dim3(256), 0, as_stream(stream), image, image_dtype,
+                           (bf16_t*)patches, B, H, W, sh, sw, top, left, OS, m, sd, bf16_ops);
+    else
+        hipLaunchKernelGGL(tv_resize_patches_kernel<false>, dim3(4096), dim3(256), 0, as_stream(stream), image, image_dtype,
+                           (bf16_t*)patches, B, H, W, sh, sw, top, left, OS, m, sd, bf16_ops);
+    ADVGRPO_LAUNCH_CHECK();
+    return 0;
+}
+
+/* the aesthetic head: embeds f32 / bf16 [N, 768] -> scores f32 [N]; w0..w4 / b0..b4 f32, row-major [out, in] (see the kernel) */
+extern "C" int advgrpo_aesthetic_head(const void* embeds, int embed_dtype, int N, const float* w0, const float* b0, const float* w1,
+                                      const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, const float* w4,
+                                      const float* b4, float* scores, void* stream) {
+    ADVGRPO_CHECK(embeds && scores && w0 && b0 && w1 && b1 && w2 && b2 && w3 && b3 && w4 && b4 && N > 0, "aesthetic_head: bad argument");
+    ADVGRPO_CHECK(embed_dtype == ADVGRPO_F32 || embed_dtype == ADVGRPO_BF16, "aesthetic_head: embeds must be f32 or bf16");
+    AesWeights wt = {{w0, w1, w2, w3, w4}, {b0, b1, b2, b3, b4}};
+    hipLaunchKernelGGL(aesthetic_head_kernel, dim3((N + AES_ROWS - 1) / AES_ROWS), dim3(256), 0, as_stream(stream), embeds, embed_dtype,
+                       N, wt, scores);
     ADVGRPO_LAUNCH_CHECK();
     return 0;
 }

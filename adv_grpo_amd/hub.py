@@ -290,6 +290,26 @@ def load_pickscore(model_dir):
     return read_tensors(model_dir, keys=set(want)), out
 
 
+def load_clip(model_dir):
+    """A transformers CLIPModel directory (openai/clip-vit-large-patch14: the aesthetic and clipscore rewards, adv_grpo/aesthetic_scorer.py,
+    adv_grpo/clip_scorer.py) -> (state dict, ClipConfig).  The same layout and checks as load_pickscore."""
+    return load_pickscore(model_dir)
+
+
+def load_aesthetic_head(path):
+    """The aesthetic predictor's state dict (sac+logos+ava1-l14-linearMSE.pth: ``layers.{0,2,4,6,7}.{weight,bias}``) -> f32 tensors,
+    read with ``torch.load(weights_only=True)`` and checked against the MLP's shapes."""
+    import torch
+    try:
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+    except Exception as e:
+        raise HubError(f"{path}: not a readable torch state dict ({type(e).__name__}: {e})") from None
+    if not isinstance(sd, dict) or not all(isinstance(v, torch.Tensor) for v in sd.values()):
+        raise HubError(f"{path}: expected a state dict of tensors")
+    validate({k: tuple(v.shape) for k, v in sd.items()}, synthetic.shapes(synthetic.aesthetic_head_weights), path)
+    return {k: v.float().contiguous() for k, v in sd.items()}
+
+
 def load_timm_dinov2(model_dir):
     """A timm hub directory of vit_base_patch14_dinov2.lvd142m (TD:589; config.json ``architecture`` + model.safetensors) -> (state dict,
     DinoConfig)."""

@@ -49,6 +49,12 @@ class ClipConfig:  # yuvalkirstain/PickScore_v1 = CLIP ViT-H/14
     eos_token_id: int = 49407
     act: str = "gelu"
 
+    @classmethod
+    def vit_l14(cls):
+        """openai/clip-vit-large-patch14: the tower of the aesthetic and clipscore rewards (its config.json keeps the legacy eos 2)."""
+        return cls(v_hidden=1024, v_layers=24, v_heads=16, v_mlp=4096, t_hidden=768, t_layers=12, t_heads=12, t_mlp=3072, proj=768,
+                   eos_token_id=2, act="quick_gelu")
+
 
 @dataclass
 class ClipTextConfig:  # SD3's text_encoder (CLIP ViT-L/14 text tower, the defaults) / text_encoder_2 (OpenCLIP bigG: ClipTextConfig.bigg())

@@ -98,7 +98,7 @@ class PickScoreScorer(torch.nn.Module):
     def __call__(self, prompt, images):
         dev = torch.device(self.device)
         if dev.type != "cuda":
-            image_embs = self.model.get_image_features(images=self._images(images))
+            image_embs = self._image_features(images)
             text_embs = self._text_features(prompt)
         else:
             main = torch.cuda.current_stream(dev)
@@ -108,12 +108,18 @@ class PickScoreScorer(torch.nn.Module):
             # image tower FIRST: its launches queue up on the device (8 ms of kernels for 3 - 4 ms of host time); the text tower's
             # launches then reach a device that is still busy and run beside it.  The other order overlaps nothing: 77-row kernels
             # finish as fast as the host can issue them.
-            image_embs = self.model.get_image_features(images=self._images(images))
+            image_embs = self._image_features(images)
             side.wait_event(ready)
             with torch.cuda.stream(side):
                 text_embs = self._text_features(prompt)
             main.wait_stream(side)
             text_embs.record_stream(main)
+        return self._scores(image_embs, text_embs)
+
+    def _image_features(self, images):
+        return self.model.get_image_features(images=self._images(images))
+
+    def _scores(self, image_embs, text_embs):
         if self.dtype == torch.float32:
             return vit_x3.pickscore_scores_f32(image_embs, text_embs, self.model.logit_scale)
         return vit.pickscore_scores(image_embs, text_embs, self.model.logit_scale)

@@ -124,3 +124,37 @@ def siglip_patches(images, size=384):
     _lib.check(lib.advgrpo_siglip_preprocess_patches(_lib.ptr(images), dt, patches.data_ptr(), B, H, W, size,
                                                      _lib.stream_ptr()))
     return patches
+
+
+def tv_resize_geometry(H, W, size=224):
+    """torchvision's integer rules for T.Resize(size) then T.CenterCrop(size) on an H x W tensor -> (RH, RW, top, left): the shorter
+    side becomes ``size``, the longer ``int(size * long / short)`` (transforms._compute_resized_output_size), and the crop starts at
+    ``int(round((R - size) / 2.0))`` (F.center_crop; Python's round, half to even)."""
+    short, long = (W, H) if W <= H else (H, W)
+    new_short, new_long = size, int(size * long / short)
+    RH, RW = (new_long, new_short) if W <= H else (new_short, new_long)
+    return RH, RW, int(round((RH - size) / 2.0)), int(round((RW - size) / 2.0))
+
+
+def tv_clip_patches(images, size=224, x3=False):
+    """ClipScorer's preprocessing (adv_grpo/clip_scorer.py): images [B,3,H,W] f32 / bf16 (used as given) or uint8 (divided by 255 in
+    f32: the ndarray path), device -> T.Resize(size) (bilinear, antialias, as torch's GPU kernel computes it) -> T.CenterCrop(size) ->
+    T.Normalize(CLIP mean / std in the image's dtype) -> bf16 [B*(size//14)^2, 640] patch rows, or with x3 the split-bf16 [B*P, 1920]
+    of the f32 values (vit_x3.py).  Only the crop window is resized; no intermediate image is stored."""
+    lib = _lib.load()
+    B, C, H, W = images.shape
+    assert C == 3
+    if images.dtype not in (torch.float32, torch.bfloat16, torch.uint8):
+        raise TypeError(f"tv_clip_patches: images must be f32, bf16 or uint8, not {images.dtype}")
+    RH, RW, top, left = tv_resize_geometry(H, W, size)
+    # T.Normalize casts mean / std to the image's dtype (a uint8 image is f32 by then)
+    cast = torch.bfloat16 if images.dtype == torch.bfloat16 else torch.float32
+    mean = torch.tensor(CLIP_MEAN, dtype=cast).float().tolist()
+    std = torch.tensor(CLIP_STD, dtype=cast).float().tolist()
+    P = (size // 14) ** 2
+    patches = torch.empty(B * P, 3 * 640 if x3 else 640, dtype=torch.bfloat16, device=images.device)
+    images = images.contiguous()
+    dt = _lib.U8 if images.dtype == torch.uint8 else _lib.dtype_code(images.dtype)
+    _lib.check(lib.advgrpo_tv_resize_patches(_lib.ptr(images), dt, patches.data_ptr(), int(x3), B, H, W, RH, RW, top, left, size,
+                                             _f3(mean), _f3(std), _lib.stream_ptr()))
+    return patches

@@ -4,9 +4,9 @@ Mirror of adv_grpo/rewards.py:1012-1095: ``multi_score(device, {name: weight}) -
 metadata, scorer=None, ref_images=None, only_strict=True, head=None, ...) -> ({name: scores, ..., 'avg':
 [...]}, {})`` with the same name-dispatched calling conventions (factory takes ``device`` iff it has a
 parameter of that name; co-train scorers receive the backbone / head as arguments).  Registered: the six
-scorers on the hot path, ``jpeg_compressibility`` (on-device JPEG, jpeg.py) and the SigLIP eval reward
-``siglip_image_similarity`` (vit.SiglipVision); the remote-server /
-VLM scorers are out of scope and raise a clear error.  New scorers can be added with ``register_scorer``.
+scorers on the hot path, ``jpeg_compressibility`` (on-device JPEG, jpeg.py), the SigLIP eval reward
+``siglip_image_similarity`` (vit.SiglipVision) and the two CLIP ViT-L/14 training rewards ``aesthetic`` (aesthetic_scorer.py) and
+``clipscore`` (clip_scorer.py); the remote-server / VLM scorers are out of scope and raise a clear error.  New scorers can be added with ``register_scorer``.
 """
 import inspect
 
@@ -14,8 +14,8 @@ import torch
 
 from . import vit
 
-_OUT_OF_SCOPE = ("deqa", "video_ocr", "imagereward", "qwenvl", "aesthetic", "unifiedreward",
-                 "geneval", "clipscore", "image_similarity_eval", "constractive_external", "discriminator",
+_OUT_OF_SCOPE = ("deqa", "video_ocr", "imagereward", "qwenvl", "unifiedreward",
+                 "geneval", "image_similarity_eval", "constractive_external", "discriminator",
                  "pickscore_patch", "dino_multi_cotrain", "siglip_cotrain")
 # scorers a shipped experiment of config/grpo.py names although they are outside SURVEY.md 8's six: why, per name
 _WHY_NOT = {
@@ -180,6 +180,58 @@ def configure_siglip(model):
     _SIGLIP["model"] = model
 
 
+_AESTHETIC = {}
+
+
+def configure_aesthetic(model, head):
+    """Weights of ``aesthetic``: ``model`` a CLIP ViT-L/14 tower (vit_x3.CLIPModelX3: the reference's fp32 arithmetic; vit.CLIPModel: bf16),
+    e.g. built from hub.load_clip or synthetic.clip_weights(ClipConfig.vit_l14()); ``head`` the MLP's state dict (hub.load_aesthetic_head,
+    synthetic.aesthetic_head_weights)."""
+    _AESTHETIC.update(model=model, head=head)
+
+
+def aesthetic_score():
+    """rewards.py:37-51: the LAION aesthetic predictor on CLIP ViT-L/14 image embeddings.  images: a device tensor [N,3,H,W] in [0,1]
+    (quantised to uint8 values in its own dtype, on the device) or an NHWC uint8 array; square images only.  -> f32 [N] on the device."""
+    from .aesthetic_scorer import AestheticScorer
+    if not _AESTHETIC:
+        raise RuntimeError("aesthetic: call rewards.configure_aesthetic(model, head) first (no checkpoint download)")
+    model = _AESTHETIC["model"]
+    scorer = AestheticScorer(dtype=torch.bfloat16 if isinstance(model, vit.CLIPModel) else torch.float32, model=model,
+                             head_sd=_AESTHETIC["head"])
+
+    def _fn(images, prompts, metadata):
+        if not isinstance(images, torch.Tensor):                                # RW:46-47: NHWC uint8 -> NCHW
+            images = torch.as_tensor(images).permute(0, 3, 1, 2)
+        return scorer(images), {}
+    return _fn
+
+
+_CLIP = {}
+
+
+def configure_clip(model):
+    """The tower of ``clipscore``: a CLIP ViT-L/14 vit_x3.CLIPModelX3 (fp32, the reference's arithmetic) or vit.CLIPModel (bf16); the
+    same object may serve ``aesthetic``."""
+    _CLIP["model"] = model
+
+
+def clip_score():
+    """rewards.py:53-66: exp(logit_scale) * cos(image, prompt) / 30 of CLIP ViT-L/14.  images: a device tensor [N,3,H,W] (used as given,
+    any size) or an NHWC uint8 array (/ 255 in f32); prompts: a PromptBatch with clip_ids (or input_ids [N,77]).  -> f32 [N]."""
+    from .clip_scorer import ClipScorer
+    model = _CLIP.get("model")
+    if model is None:
+        raise RuntimeError("clipscore: call rewards.configure_clip(model) first (no checkpoint download)")
+    scorer = ClipScorer(dtype=torch.bfloat16 if isinstance(model, vit.CLIPModel) else torch.float32, model=model)
+
+    def _fn(images, prompts, metadata):
+        if not isinstance(images, torch.Tensor):                                # RW:59-61: NHWC uint8 -> NCHW, / 255 in the kernel
+            images = torch.as_tensor(images).permute(0, 3, 1, 2)
+        return scorer(images, prompts), {}
+    return _fn
+
+
 _OCR = {}
 
 
@@ -233,6 +285,8 @@ score_functions = {
     "dino_patch_cotrain": dino_patch_cotrain_score,
     "jpeg_compressibility": jpeg_compressibility,
     "siglip_image_similarity": siglip_image_similarity_score,
+    "aesthetic": aesthetic_score,
+    "clipscore": clip_score,
 }
 
 

@@ -393,6 +393,21 @@ def dino_head_weights(in_dim=768, hidden=512, seed=999):
     return W
 
 
+AESTHETIC_HEAD_DIMS = (768, 1024, 128, 64, 16, 1)
+AESTHETIC_HEAD_LAYERS = (0, 2, 4, 6, 7)        # the nn.Sequential indices of the five Linears (Dropouts at 1, 3, 5)
+
+
+def aesthetic_head_weights(seed=1213):
+    """The LAION improved-aesthetic MLP (adv_grpo/aesthetic_scorer.py, sac+logos+ava1-l14-linearMSE.pth): fp32 ``layers.{0,2,4,6,7}``
+    Linears 768 -> 1024 -> 128 -> 64 -> 16 -> 1."""
+    g = _gen(seed)
+    W = {}
+    for i, (fi, fo) in zip(AESTHETIC_HEAD_LAYERS, zip(AESTHETIC_HEAD_DIMS[:-1], AESTHETIC_HEAD_DIMS[1:])):
+        # the inputs are unit vectors: a first layer of std 1 keeps the activations O(1), as in dino_head_weights
+        linear_(W, f"layers.{i}", fo, fi, g, std=1.0 if i == 0 else None)
+    return W
+
+
 def clip_input_ids(n, seed=3, vocab=49408, eos=49407, length=77):
     """Synthetic CLIP token ids: random tokens, EOS at a random position >= 8, pad (= EOS) after."""
     g = torch.Generator().manual_seed(seed)

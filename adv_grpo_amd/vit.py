@@ -104,7 +104,7 @@ def _pad_patch_weight(w, dev):
 
 
 class CLIPModel:
-    """PickScore_v1 / CLIP ViT-H/14 with transformers state_dict names."""
+    """PickScore_v1 / CLIP ViT-H/14 (or CLIP ViT-L/14: ClipConfig.vit_l14()) with transformers state_dict names."""
 
     def __init__(self, sd, cfg, device="cuda"):
         self.cfg, dev = cfg, torch.device(device)
@@ -112,7 +112,7 @@ class CLIPModel:
         self.logit_scale = sd["logit_scale"].float().cpu()      # a host scalar: read by every scoring call (no device -> host copy there)
 
         layers = lambda pfx, n: pack_clip_layers(sd, pfx, n, dev)
-        act = "gelu"
+        act = "quick_gelu" if getattr(cfg, "act", "gelu") == "quick_gelu" else "gelu"     # CLIP ViT-L/14: quick_gelu; PickScore: gelu
         v, t = "vision_model", "text_model"
         self.v_enc = _Encoder(layers(v, cfg.v_layers), cfg.v_heads, 1e-5, act)
         self.t_enc = _Encoder(layers(t, cfg.t_layers), cfg.t_heads, 1e-5, act, causal=True)

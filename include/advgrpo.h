@@ -732,6 +732,26 @@ int advgrpo_jpeg_encode(const void* images, int dtype, int layout, int N, int H,
  * advgrpo_attention_fwd (head dim 72; its attention-pooling head passes Sq = 1 and a q batch stride of 0). */
 int advgrpo_siglip_preprocess_patches(const void* image, int image_dtype, void* patches, int B, int H, int W, int OS, void* stream);
 
+
+/* ------------------------------------------------------------------ CLIP ViT-L/14 (aesthetic and clipscore rewards)
+ * Preprocessing of ClipScorer (adv_grpo/clip_scorer.py): torchvision T.Resize(OS) -> T.CenterCrop(OS) -> T.Normalize on a tensor.
+ * image [B,3,H,W] F32 / BF16 / U8 (U8: x / 255 in f32 first, the ndarray path) is resized to RH x RW by torch's GPU
+ * upsample_bilinear2d_aa arithmetic (f32 weights and sums, horizontal pass then vertical); only the OS x OS window at (top, left) is
+ * computed.  RH, RW, top, left are the caller's (torchvision's integer rules).  Then (x - mean) / std in f32; for a BF16 image the
+ * resize result, the difference and the quotient are each rounded to bf16 and mean3 / std3 must hold bf16 values.
+ * patches: x3 = 0: bf16 [B*P, 640] im2col rows of the 14/14 patch conv (588 real columns + zeros), P = (OS/14)^2;
+ *          x3 = 1: the split-bf16 left operand [B*P, 3*640] ([hi | hi | lo] of the f32 values). */
+int advgrpo_tv_resize_patches(const void* image, int image_dtype, void* patches, int x3, int B, int H, int W, int RH, int RW, int top,
+                              int left, int OS, const float* mean3_host, const float* std3_host, void* stream);
+
+/* The LAION aesthetic predictor head (adv_grpo/aesthetic_scorer.py): e / ||e||_2 -> Linear(768,1024) -> Linear(1024,128) ->
+ * Linear(128,64) -> Linear(64,16) -> Linear(16,1), no activations.  embeds F32 / BF16 [N, 768] rows; w_l f32 [out, in] row-major,
+ * b_l f32 [out]; scores f32 [N].  f32 products and sums in a fixed order (no atomics): a row's score does not depend on N or on
+ * where the row sits in the batch. */
+int advgrpo_aesthetic_head(const void* embeds, int embed_dtype, int N, const float* w0, const float* b0, const float* w1, const float* b1,
+                           const float* w2, const float* b2, const float* w3, const float* b3, const float* w4, const float* b4,
+                           float* scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

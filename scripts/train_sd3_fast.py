@@ -10,6 +10,8 @@
 
   python scripts/train_sd3_fast.py --config ... --weights <local snapshot of config.pretrained.model> \
          --pickscore-weights <PickScore_v1 dir> | --dino-weights <timm vit_base_patch14_dinov2 dir>      (real checkpoints, adv_grpo_amd/hub.py)
+  python scripts/train_sd3_fast.py --config ... --reward-fn aesthetic=1 --clip-l-weights <clip-vit-large-patch14 dir> \
+         --aesthetic-head <sac+logos+ava1-l14-linearMSE.pth>      (clipscore=1 needs --clip-l-weights only)
 
 No checkpoints / tokenizers / reference images exist on this platform: without --weights the models get seeded synthetic weights of the
 real architecture and data comes from trainer.SyntheticData.  With --weights every component's config.json and every tensor
@@ -73,6 +75,11 @@ def main():
                          "StableDiffusion3Pipeline.from_pretrained (TP:447-449) would have downloaded; validated and loaded by adv_grpo_amd/hub.py")
     ap.add_argument("--pickscore-weights", default=None, help="local directory of yuvalkirstain/PickScore_v1 (a transformers CLIPModel; pickscore_scorer.py:8-14)")
     ap.add_argument("--dino-weights", default=None, help="local timm directory of vit_base_patch14_dinov2.lvd142m (TD:589)")
+    ap.add_argument("--clip-l-weights", default=None, metavar="DIR",
+                    help="local directory of openai/clip-vit-large-patch14 (a transformers CLIPModel): the tower of the aesthetic and "
+                         "clipscore rewards")
+    ap.add_argument("--aesthetic-head", default=None, metavar="FILE",
+                    help="the aesthetic predictor's sac+logos+ava1-l14-linearMSE.pth (needed by the aesthetic reward)")
     args = ap.parse_args()
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     from adv_grpo_amd.config.experiments import parse_config_flag
@@ -88,6 +95,12 @@ def main():
                              "scoring passes none (neither does the reference, TD:901): it is an eval reward (Trainer.evaluate)")
         if rname not in _rw.score_functions:
             raise SystemExit(f"{args.config}: unknown reward '{rname}' (registered: {', '.join(sorted(_rw.score_functions))})")
+        # CLIP ViT-L/14 rewards: real weights only (no synthetic stand-in: a random tower's scores would train on noise)
+        missing = [f for f, v in (("--clip-l-weights DIR", args.clip_l_weights), ("--aesthetic-head FILE", args.aesthetic_head))
+                   if v is None and (rname == "aesthetic" or (rname == "clipscore" and f.startswith("--clip-l")))]
+        if missing:
+            raise SystemExit(f"{args.config}: reward '{rname}' needs " + " and ".join(missing) +
+                             " (openai/clip-vit-large-patch14" + (" and the aesthetic predictor head" if rname == "aesthetic" else "") + ")")
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
     if world > 1:
@@ -180,6 +193,14 @@ def main():
             rewards.configure_pickscore(synthetic.clip_weights(ClipConfig(), 777), ClipConfig())
         if "image_similarity" in wanted:
             rewards.configure_dino(vit_x3.DinoV2X3(synthetic.dino_weights(DinoConfig(), 888), DinoConfig(), device))
+    if wanted & {"aesthetic", "clipscore"} and args.clip_l_weights:
+        from adv_grpo_amd import hub
+        lw, lcfg = hub.load_clip(args.clip_l_weights)
+        clip_l = vit_x3.CLIPModelX3(lw, lcfg, device)             # the reference's fp32 ViT-L/14 (rewards.py:40, 58)
+        del lw
+        rewards.configure_clip(clip_l)
+        if args.aesthetic_head:
+            rewards.configure_aesthetic(clip_l, hub.load_aesthetic_head(args.aesthetic_head))
     if "ocr" in wanted:
         try:
             import paddleocr  # noqa: F401  (adv_grpo/ocr.py:8-65 uses it when present)
