@@ -155,6 +155,12 @@ SIGNATURES = {
     "advgrpo_mmdit_block_backward": (c_int, [POINTER(MMDiTBlockBwdDesc), _P, c_int64, _P]),
     "advgrpo_vae_decode_workspace_bytes": (c_int64, [POINTER(VaeDecoderDesc)]),
     "advgrpo_vae_decode": (c_int, [POINTER(VaeDecoderDesc), _P, c_int, _P, _P, c_int64, _P]),
+    "advgrpo_conv3x3_s2_nhwc_x3": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "advgrpo_image_to_nhwc_x3": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, _P]),
+    "advgrpo_vae_latent_tail": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_uint64, c_uint64, c_float, _P, c_int, c_int, _P, c_int,
+                                        c_uint64, c_uint64, _P, _P, _P]),
+    "advgrpo_vae_encode_workspace_bytes": (c_int64, [POINTER(VaeDecoderDesc)]),
+    "advgrpo_vae_encode": (c_int, [POINTER(VaeDecoderDesc), _P, c_int, _P, _P, c_int64, _P]),
     "advgrpo_vit_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "advgrpo_vit_forward": (c_int, [POINTER(VitDesc), _P, c_int64, _P]),
     "advgrpo_gemm_tn_grouped_workspace_bytes": (c_int64, [POINTER(TnDesc), c_int]),

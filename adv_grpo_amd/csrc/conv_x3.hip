@@ -93,12 +93,19 @@ __device__ __forceinline__ void x3_tie(bf16x8_t (&a)[N]) {
 // tiles deep: a wave tile of 48 x 128 (96 MFMAs per wave behind one barrier per k-tile instead of 48; the same pixel stage feeds twice the
 // channels: 26 % fewer L2 -> LDS bytes and 30 % fewer fragment bytes per flop); the weight ring then holds three one-piece stages of 32 KiB
 // (the same 146 KiB).  Same k order and product order per output element as BN = 128: the same bits.
-template <int X3_WM, int X3_WN, int DBG = 0, int PIECE = 0, int BN = X3_BN>
+// S2 (the VAE encoder's Downsample2D): stride 2 over an input of twice the output's height and width, zero-padded by one row below and one
+// column to the right -- output pixel (y, x), tap (ky, kx) reads input pixel (2 y + ky, 2 x + kx), the zero page when that is row 2 Hout or
+// column 2 Wout.  Consecutive output pixels are no longer consecutive input pixels, so the three taps of a kernel row cannot share one
+// shifted pixel stage: EVERY k-tile stages its own 192 pixels and runs as the last tap of a group does below (all pixel fragments into
+// registers, barrier, the next k-tile's pixel stage behind it, then the weight prefetch two k-tiles ahead).  No edge masks: the padding is
+// in the addressing.  Same tile, same MFMA, same k order (ky, 64-channel slice, kx) and product order per output element.
+template <int X3_WM, int X3_WN, int DBG = 0, int PIECE = 0, int BN = X3_BN, bool S2 = false>
 __global__ __launch_bounds__(64 * X3_WM * X3_WN, 1) void conv3x3_x3_kernel(const GemmParams p) {
     constexpr bool F16 = PIECE != 0;                  // one-piece weights, two products (1: fp16 pieces; 2: bf16 pieces; 3: fp16 pieces, hi product only)
     constexpr bool X1 = PIECE == 3;
     constexpr int WPI = F16 ? 1 : 2;                  // weight pieces per tap (DMA instructions per 8 output channels)
     constexpr int NW = X3_WM * X3_WN, TM = X3_BM / X3_WM, TN = BN / X3_WN, FM = TM / 16, FN = TN / 16;
+    static_assert(!S2 || (PIECE == 0 && DBG == 0), "the strided form exists for the three-product arithmetic");
     static_assert(BN == X3_BN || PIECE != 0, "the wide tile exists for the one-piece-weight forms");
     constexpr int WPIECE = BN * X3_BK * 2;            // one weight piece of one tap: BN output channels x 64 input channels
     constexpr int WSTAGE = (BN == X3_BN ? 2 : 1) * WPIECE;
@@ -128,7 +135,7 @@ __global__ __launch_bounds__(64 * X3_WM * X3_WN, 1) void conv3x3_x3_kernel(const
         const int bi = q / hw, rem = q - bi * hw;
         a_y[it] = rem / p.Wout;
         a_x[it] = rem - a_y[it] * p.Wout;
-        a_img[it] = (int64_t)bi * (p.Hout >> p.ups) * (p.Wout >> p.ups) * p.Cin;
+        a_img[it] = S2 ? (int64_t)bi * (2 * p.Hout) * (2 * p.Wout) * p.Cin : (int64_t)bi * (p.Hout >> p.ups) * (p.Wout >> p.ups) * p.Cin;
     }
     const bf16_t* w_src[WI];
 #pragma unroll
@@ -158,6 +165,24 @@ __global__ __launch_bounds__(64 * X3_WM * X3_WN, 1) void conv3x3_x3_kernel(const
             if constexpr (!X1) __builtin_amdgcn_global_load_lds((x3_gptr_t)lo, (x3_lds_ptr_t)(dst + X3_XPIECE), 16, 0, 0);
         }
     };
+    // strided form: the pixel stage of k-tile kt = (g, kx) -- LDS row j = input pixel (2 y + ky, 2 x + kx) of output pixel m0 - 1 + j
+    auto stage_x_s2 = [&](int kt) {
+        const int g = kt / 3, kx = kt - 3 * g;
+        const int dyi = g / slices, c0 = (g - dyi * slices) * X3_BK;
+        const int hin = 2 * p.Hout, wi2 = 2 * p.Wout;
+#pragma unroll
+        for (int it = 0; it < XI; ++it) {
+            if (wave + it * NW >= X3_XINST) break;    // wave-uniform
+            const int yy = 2 * a_y[it] + dyi, xx = 2 * a_x[it] + kx;
+            const bool ok = yy < hin && xx < wi2;     // row 2 Hout / column 2 Wout: the (0, 1, 0, 1) zero padding
+            const bf16_t* hi = ok ? p.A + a_img[it] + ((int64_t)yy * wi2 + xx) * p.Cin + c0 + schunk * 8 : p.zero_page + schunk * 8;
+            const bf16_t* lo = ok ? hi + 2 * C : hi;
+            char* dst = smem + (wave + it * NW) * 1024;
+            __builtin_amdgcn_global_load_lds((x3_gptr_t)hi, (x3_lds_ptr_t)dst, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((x3_gptr_t)lo, (x3_lds_ptr_t)(dst + X3_XPIECE), 16, 0, 0);
+        }
+    };
+    (void)stage_x; (void)stage_x_s2;             // (one of the two per instantiation)
     auto stage_w = [&](int buf, int g, int dxi) {
         char* base = smem + X3_XSTAGE + buf * WSTAGE;
         const int dyi = g / slices, c0 = (g - dyi * slices) * X3_BK;
@@ -203,7 +228,8 @@ __global__ __launch_bounds__(64 * X3_WM * X3_WN, 1) void conv3x3_x3_kernel(const
     // Waits are counted by hand (raw s_barrier: __syncthreads() would drain every LDS-DMA): a wave has 2 * WI = 4 weight
     // instructions per k-tile in flight behind whatever the next k-tile reads.
     const int ngroups = 3 * slices, nk = 3 * ngroups;
-    stage_x(0);
+    if constexpr (S2) stage_x_s2(0);
+    else stage_x(0);
     stage_w(0, 0, 0);
     stage_w(1, 0, 1);
     asm volatile("s_waitcnt vmcnt(%0)" : : "n"(WPI * WI) : "memory");
@@ -264,7 +290,32 @@ __global__ __launch_bounds__(64 * X3_WM * X3_WN, 1) void conv3x3_x3_kernel(const
             bf16x8_t ah0[FM], al0[FM], bh0[FN], bl0[FN], ah1[FM], al1[FM], bh1[FN], bl1[FN];
             const bool more = kt + 2 < nk;                   // (then group g + 1 exists as well when dxi == 2)
             const bool rd = DBG != 3 || kt == 0;
-            if constexpr (X1 && dxi < 2) {
+            if constexpr (S2) {
+                // every k-tile has a pixel stage of its own, held at the un-shifted rows (xa[1]): the form of a group's last tap below
+                (void)mask; (void)rd;
+                read_x(xa[1][0], ah0, al0, true, true); read_x(xa[1][1], ah1, al1, true, true);
+                read_wl(wb0, bl0);
+                x3_wait_reads<FN>(); x3_tie(ah0); x3_tie(al0); x3_tie(ah1); x3_tie(al1);
+                __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_sched_barrier(0);
+                if (kt + 1 < nk) stage_x_s2(kt + 1);
+                if (more) stage_w((dxi + 2) % 3, (kt + 2) / 3, (dxi + 2) % 3);
+                __builtin_amdgcn_sched_barrier(0);
+                read_wh(wb0, bh0); read_wl(wb1, bl1); read_wh(wb1, bh1);
+                x3_wait_reads<3 * FN>(); x3_tie(bl0);
+                product(ah0, bl0);
+                __builtin_amdgcn_sched_barrier(0);
+                x3_wait_reads<2 * FN>(); x3_tie(bh0);
+                product(al0, bh0);
+                product(ah0, bh0);
+                __builtin_amdgcn_sched_barrier(0);
+                x3_wait_reads<FN>(); x3_tie(bl1);
+                product(ah1, bl1);
+                __builtin_amdgcn_sched_barrier(0);
+                x3_wait_reads<0>(); x3_tie(bh1);
+                product(al1, bh1);
+                product(ah1, bh1);
+            } else if constexpr (X1 && dxi < 2) {
                 // hi product only: both 32-deep steps' x_hi and w fragments requested up front
                 if (rd) { read_x(xa[dxi][0], ah0, al0, true, false); read_wh(wb0, bh0); read_x(xa[dxi][1], ah1, al1, true, false); read_wh(wb1, bh1); }
                 __builtin_amdgcn_sched_barrier(0);
@@ -494,9 +545,22 @@ int conv3x3_f16x2_launch(const GemmParams& p, hipStream_t s, int form /* 0: f16x
 
 // p as filled by advgrpo_conv3x3_nhwc_x3 (gemm.hip): Cin = 3C, K = 9 * 3C, lda = 3C, ldw = 27C, f32_io
 int conv3x3_x3_launch(const GemmParams& p, hipStream_t s) {
-    ADVGRPO_CHECK(p.conv && p.f32_io && p.Cin % 192 == 0 && p.zero_page && p.batch == 1 && p.splitk == 1,
+    ADVGRPO_CHECK(p.conv && p.f32_io && p.Cin % 192 == 0 && p.zero_page && p.batch == 1 && p.splitk == 1 && !(p.stride2 && p.ups),
                   "conv3x3_x3: bad parameter block");
     constexpr int WM = X3_GRID_M, WN = X3_GRID_N;
+    if (p.stride2) {
+        static bool s2_attr_set = false;
+        if (!s2_attr_set) {
+            ADVGRPO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_x3_kernel<WM, WN, 0, 0, X3_BN, true>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS) == hipSuccess,
+                          "conv3x3_s2_x3: %d bytes of LDS refused", X3_LDS);
+            s2_attr_set = true;
+        }
+        const int s2_tiles = ((p.M + X3_BM - 1) / X3_BM) * ((p.N + X3_BN - 1) / X3_BN);
+        hipLaunchKernelGGL((conv3x3_x3_kernel<WM, WN, 0, 0, X3_BN, true>), dim3(s2_tiles), dim3(64 * WM * WN), X3_LDS, s, p);
+        ADVGRPO_LAUNCH_CHECK();
+        return 0;
+    }
     static bool attr_set = false;
     if (!attr_set) {
         ADVGRPO_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_x3_kernel<WM, WN, 0>),

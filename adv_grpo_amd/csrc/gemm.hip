@@ -594,3 +594,25 @@ extern "C" int advgrpo_conv3x3_nhwc_x3(const void* x3, const void* w3, float* y,
     if (Cout >= 128) return conv3x3_x3_launch(p, as_stream(stream));
     return gemm_bf16(p, as_stream(stream));
 }
+
+/* Downsample2D(padding=0) of the VAE encoder over split operands: F.pad(x, (0, 1, 0, 1)) + 3x3 convolution of stride 2 without padding.
+ * x3 [B, 2 Hout, 2 Wout, Cin3 = 3C] ([hi | . | lo]: the middle third is not read), w3 as advgrpo_conv3x3_nhwc_x3; bias, y f32 */
+extern "C" int advgrpo_conv3x3_s2_nhwc_x3(const void* x3, const void* w3, float* y, int B, int Hout, int Wout, int Cin3, int Cout,
+                                          const float* bias, const void* zero_page, void* stream) {
+    ADVGRPO_CHECK(x3 && w3 && y && zero_page, "conv3x3_s2_x3: null pointer");
+    ADVGRPO_CHECK(B > 0 && Hout > 0 && Wout > 0 && (int64_t)B * Hout * Wout < (1ll << 31), "conv3x3_s2_x3: bad shape (B=%d Hout=%d Wout=%d)", B, Hout, Wout);
+    ADVGRPO_CHECK(Cin3 > 0 && Cin3 % 192 == 0 && Cout >= 128 && Cout % 4 == 0,
+                  "conv3x3_s2_x3: Cin3 must be 3 x (a multiple of 64), Cout >= 128 and a multiple of 4 (Cin3=%d Cout=%d)", Cin3, Cout);
+    GemmParams p{};
+    p.A = (const bf16_t*)x3; p.W = (const bf16_t*)w3; p.C = y;
+    p.lda = Cin3; p.ldw = 9 * (int64_t)Cin3; p.ldc = Cout; p.out_dtype = ADVGRPO_F32;
+    p.M = B * Hout * Wout; p.N = Cout; p.K = 9 * Cin3;
+    p.bias = (const bf16_t*)bias; p.act = 0; p.alpha = 1.0f;
+    p.ldr = Cout;
+    p.batch = 1;
+    p.conv = 1; p.Hout = Hout; p.Wout = Wout; p.Cin = Cin3; p.ups = 0; p.stride2 = 1;
+    p.zero_page = (const bf16_t*)zero_page;
+    p.splitk = 1;
+    p.f32_io = 1;
+    return conv3x3_x3_launch(p, as_stream(stream));
+}

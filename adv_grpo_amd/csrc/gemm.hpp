@@ -48,6 +48,9 @@ struct GemmParams {
     // f16x2 convolution only: INSTEAD of the f32 output, the fp16-pair rows [hi | unwritten | lo] of pair_prescale * y (the operand form of
     // the next f16x2 convolution when nothing else reads y: a resnet's conv2 in front of an upsampler) -- pair_out [M, 3 N] 16-bit
     void* pair_out; float pair_prescale;
+    // split-bf16 convolution only (conv_x3.hip): stride 2 over an input [B, 2 Hout, 2 Wout, Cin] zero-padded by one row below and one column to
+    // the right (diffusers' Downsample2D(padding=0): F.pad(x, (0, 1, 0, 1)) + a 3x3 convolution of stride 2 without padding); ups must be 0
+    int stride2;
     int debug;   // experiments only (ADVGRPO_GEMM_DEBUG): bit0 = skip steady-state DMA, bit1 = skip LDS fragment reads
 };
 

@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "vae_chain.hpp"
 
 using namespace advgrpo;
 
@@ -24,7 +25,8 @@ namespace {
 constexpr float RAW_PRESCALE = 0.0625f;     // 2^-4: un-normalised convolution inputs (the upsamplers') as fp16 pairs stay in range
 constexpr int STAT_ROWS = 16;               // ADVGRPO_CONV_F16X2_STAT_ROWS: pixels per block sum of the convolution epilogue
 
-int64_t piece(int64_t bytes) { return (bytes + 255) / 256 * 256; }
+using vae_chain::piece;
+using vae_chain::vae_mid_attention;
 
 struct Plan {                                // workspace sizes from one walk over the architecture
     int64_t max_elems = 0;                   // largest f32 activation [B, H, W, C]
@@ -174,33 +176,8 @@ extern "C" int advgrpo_vae_decode(const advgrpo_vae_decoder_desc* dsc, const voi
         // behind the output to the end of the pair rows is free until the next convolution (Plan)
         ADVGRPO_CHECK(x.slot == 1, "vae_decode: internal slot order changed");
         char* a = attn_extra ? attn_extra : reinterpret_cast<char*>(act[2]) + piece(M * C * 4);
-        auto tk = [&](int64_t bytes) { char* p = a; a += piece(bytes); return p; };
-        char* h3 = tk(M * 3 * C * 2); char* q3 = tk(M * 3 * C * 2); char* k3 = tk(M * 3 * C * 2); char* o3 = tk(M * 3 * C * 2);
-        float* q = reinterpret_cast<float*>(tk(M * C * 4)); float* k = reinterpret_cast<float*>(tk(M * C * 4));
-        float* o = reinterpret_cast<float*>(tk(M * C * 4)); float* y = reinterpret_cast<float*>(tk(M * C * 4));
-        float* vt = reinterpret_cast<float*>(tk((int64_t)B * C * T * 4)); char* vt3 = tk((int64_t)B * C * 3 * T * 2);
-        float* s = plan.s_in_slot0 ? act[0] : reinterpret_cast<float*>(tk((int64_t)B * T * T * 4));
-        char* p3 = tk((int64_t)B * T * 3 * T * 2);
-        auto gemm_f32 = [&](const void* A, int64_t lda, const void* Wt, int64_t ldw, float* Cc, int64_t ldc, int Mm, int N, int K, float alpha, int batch,
-                            int64_t sA, int64_t sW, int64_t sC) {
-            return advgrpo_gemm_bf16(A, lda, Wt, ldw, Cc, ldc, ADVGRPO_F32, Mm, N, K, nullptr, 0, alpha, nullptr, 0, 0, nullptr, 0, 0, 0, 0, 0, 0, 0, batch, sA, sW, sC,
-                                     stream);
-        };
-        if ((rc = advgrpo_groupnorm_nhwc_x3(act[x.slot], h3, gn, d.attn_norm_w, d.attn_norm_b, B, (int)T, C, G, 1e-6f, 0, 0, stream)) != 0) return rc;
-        if ((rc = gemm_f32(h3, 3 * C, d.attn_q_w, 3 * C, q, C, (int)M, C, 3 * C, 1.0f, 1, 0, 0, 0)) != 0) return rc;
-        if ((rc = advgrpo_split_bf16x3(q, d.attn_q_b, q3, M, C, 0, stream)) != 0) return rc;
-        if ((rc = gemm_f32(h3, 3 * C, d.attn_k_w, 3 * C, k, C, (int)M, C, 3 * C, 1.0f, 1, 0, 0, 0)) != 0) return rc;
-        if ((rc = advgrpo_split_bf16x3(k, d.attn_k_b, k3, M, C, 1, stream)) != 0) return rc;
-        // V^T[b] = Wv . h[b]^T (the bias is added after P . V: rows of P sum to one); the weight is the [hi | lo | hi] side
-        if ((rc = gemm_f32(d.attn_v_w, 3 * C, h3, 3 * C, vt, T, C, (int)T, 3 * C, 1.0f, B, 0, T * 3 * C, (int64_t)C * T)) != 0) return rc;
-        if ((rc = advgrpo_split_bf16x3(vt, nullptr, vt3, (int64_t)B * C, (int)T, 1, stream)) != 0) return rc;
-        if ((rc = gemm_f32(q3, 3 * C, k3, 3 * C, s, T, (int)T, (int)T, 3 * C, (float)pow((double)C, -0.5), B, T * 3 * C, T * 3 * C, T * T)) != 0) return rc;
-        if ((rc = advgrpo_softmax_rows_x3(s, p3, M, (int)T, stream)) != 0) return rc;
-        if ((rc = gemm_f32(p3, 3 * T, vt3, 3 * T, o, C, (int)T, C, (int)(3 * T), 1.0f, B, T * 3 * T, (int64_t)C * 3 * T, T * C)) != 0) return rc;
-        if ((rc = advgrpo_split_bf16x3(o, d.attn_v_b, o3, M, C, 0, stream)) != 0) return rc;
-        if ((rc = gemm_f32(o3, 3 * C, d.attn_o_w, 3 * C, y, C, (int)M, C, 3 * C, 1.0f, 1, 0, 0, 0)) != 0) return rc;
         const int ns = 2;
-        if ((rc = advgrpo_add_rows_f32(y, act[x.slot], d.attn_o_b, act[ns], M, C, stream)) != 0) return rc;
+        if ((rc = vae_mid_attention(d, B, H, W, C, act[x.slot], act[ns], a, plan.s_in_slot0 ? act[0] : nullptr, gn, stream)) != 0) return rc;
         x = Act{ns, nullptr};
     }
     if ((rc = resnet(d.mid[1], x, false, x)) != 0) return rc;

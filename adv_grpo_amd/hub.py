@@ -231,6 +231,29 @@ def load_vae_decoder(component_dir):
     return {k: v.reshape(want[k]).float() for k, v in sd.items()}, out
 
 
+def _vae_rename_encoder(k):
+    """encoder.* with the same legacy attention names; decoder / quant convs are not on this path."""
+    return _vae_rename("decoder." + k[len("encoder."):]).replace("decoder.", "encoder.", 1) if k.startswith("encoder.") else None
+
+
+def load_vae_encoder(component_dir):
+    """AutoencoderKL of SD3 / SD3.5 -> (encoder.* state dict upcast to float32 as ``vae.to(torch.float32)`` does (TP:481), VaeConfig): the
+    encoder half of the checkpoint load_vae_decoder reads (image_to_latent, PF:703).  The moments leave conv_out directly: a checkpoint with
+    a quant_conv behind it (use_quant_conv, diffusers' default) is refused."""
+    cfg = read_config(component_dir)
+    _class(cfg, component_dir, "AutoencoderKL")
+    _expect(cfg, component_dir, _defaults=dict(act_fn="silu", use_quant_conv=True, mid_block_add_attention=True, in_channels=3),
+            act_fn="silu", use_quant_conv=False, mid_block_add_attention=True, in_channels=3)
+    out = VaeConfig(latent_channels=int(cfg["latent_channels"]), block_out_channels=tuple(cfg["block_out_channels"]),
+                    layers_per_block=int(cfg["layers_per_block"]), norm_num_groups=int(cfg["norm_num_groups"]),
+                    scaling_factor=float(cfg["scaling_factor"]), shift_factor=float(cfg.get("shift_factor") or 0.0))
+    want = synthetic.shapes(synthetic.vae_encoder_weights, out)
+    have = {n: _vae_shape(n, s) for n, s in ((_vae_rename_encoder(k), s) for k, s in header_shapes(component_dir).items()) if n is not None}
+    validate(have, want, component_dir)
+    sd = read_tensors(component_dir, keys=set(want), rename=_vae_rename_encoder)
+    return {k: v.reshape(want[k]).float() for k, v in sd.items()}, out
+
+
 def load_clip_text(component_dir):
     """CLIPTextModelWithProjection (text_encoder / text_encoder_2) -> (state dict, ClipTextConfig)."""
     cfg = read_config(component_dir)

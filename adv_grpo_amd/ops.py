@@ -581,6 +581,66 @@ def conv3x3_x3(x3, w3, bias=None, upsample=False, act=None, residual=None):
     return y
 
 
+def conv3x3_s2_x3(x3, w3, bias=None):
+    """Downsample2D(padding=0): F.pad(x, (0, 1, 0, 1)) + 3x3 convolution of stride 2.  x3 NHWC split bf16 [B,Hin,Win,3C] (Hin, Win even; the hi
+    and lo thirds are read), w3 [Cout, 9*3C], bias f32 -> f32 [B,Hin/2,Win/2,Cout]."""
+    lib = _lib.load()
+    B, Hin, Win, Cin3 = x3.shape
+    assert Hin % 2 == 0 and Win % 2 == 0 and x3.dtype == torch.bfloat16
+    assert bias is None or bias.dtype == torch.float32
+    Cout = w3.shape[0]
+    y = torch.empty(B, Hin // 2, Win // 2, Cout, dtype=torch.float32, device=x3.device)
+    with _Prof(B * (Hin // 2) * (Win // 2), Cout, 9 * Cin3, 1, 1):
+      _lib.check(lib.advgrpo_conv3x3_s2_nhwc_x3(_lib.ptr(x3), _lib.ptr(w3), y.data_ptr(), B, Hin // 2, Win // 2, Cin3, Cout, _lib.ptr(bias),
+                                              zero_page(x3.device).data_ptr(), _lib.stream_ptr()))
+    return y
+
+
+def image_to_nhwc_x3(images, cpad=64):
+    """[B,3,H,W] in [0,1] (f32 / bf16) or uint8 [B,H,W,3] -> (x - 0.5) / 0.5 as split rows [B,H,W,3*cpad] ([hi | unwritten | lo], channels >= 3 zero)."""
+    lib = _lib.load()
+    images = images.contiguous()
+    if images.dtype == torch.uint8:
+        B, H, W, c = images.shape
+        code = _lib.U8
+    else:
+        B, c, H, W = images.shape
+        code = _lib.dtype_code(images.dtype)
+    assert c == 3
+    out = torch.empty(B, H, W, 3 * cpad, dtype=torch.bfloat16, device=images.device)
+    _lib.check(lib.advgrpo_image_to_nhwc_x3(_lib.ptr(images), code, out.data_ptr(), B, H, W, cpad, _lib.stream_ptr()))
+    return out
+
+
+def vae_latent_tail(moments, scaling_factor, mode="mean", eps=None, seed=0, offset=0, out_dtype=torch.bfloat16, want_z=True,
+                    sigma=None, mix_noise=None, mix_seed=None, mix_offset=0):
+    """moments f32 NHWC [B,h,w,2C] -> latents * scaling_factor [B,C,h,w] in out_dtype (mode "mean" / "eps" (given) / "philox").
+    sigma (device f32 scalar tensor) asks for the forward noising (1 - sigma) * z + sigma * noise in bf16 arithmetic in the same launch
+    (noise = mix_noise, or Philox under (mix_seed, mix_offset)); returns z, or (z, mix)."""
+    lib = _lib.load()
+    assert moments.dtype == torch.float32 and moments.is_contiguous()
+    B, h, w, C2 = moments.shape
+    C = C2 // 2
+    m = {"mean": 0, "eps": 1, "philox": 2}[mode]
+    if m == 1:
+        assert eps is not None and eps.dtype == torch.float32 and eps.is_contiguous() and tuple(eps.shape) == (B, C, h, w)
+    z = torch.empty(B, C, h, w, dtype=out_dtype, device=moments.device) if want_z else None
+    mix, mm = None, 0
+    if sigma is not None:
+        assert sigma.dtype == torch.float32 and sigma.is_cuda and sigma.numel() == 1
+        mix = torch.empty(B, C, h, w, dtype=torch.bfloat16, device=moments.device)
+        mm = 1 if mix_noise is not None else 2
+        if mm == 1:
+            assert mix_noise.is_contiguous() and tuple(mix_noise.shape) == (B, C, h, w)
+        else:
+            assert mix_seed is not None
+    _lib.check(lib.advgrpo_vae_latent_tail(moments.data_ptr(), B, C, h, w, m, _lib.ptr(eps) if m == 1 else None, int(seed), int(offset),
+                                           float(scaling_factor), _lib.ptr(z), _lib.dtype_code(out_dtype), mm,
+                                           _lib.ptr(mix_noise) if mm == 1 else None, _lib.dtype_code(mix_noise.dtype) if mm == 1 else 0,
+                                           int(mix_seed or 0), int(mix_offset), _lib.ptr(sigma), _lib.ptr(mix), _lib.stream_ptr()))
+    return z if sigma is None else (z, mix)
+
+
 def groupnorm_nhwc_x3(x, weight, bias, groups=32, eps=1e-6, silu=False, pair_only=False):
     """f32 NHWC in, f32 affine -> split bf16 [..., 3C]; pair_only: the middle third stays unwritten (the output feeds
     conv3x3_x3 with Cout >= 128, which reads hi and lo only)."""

@@ -1,5 +1,6 @@
 """The pipeline object the rollout function takes as ``self`` (what StableDiffusion3Pipeline is to the
-reference, scripts/train_sd3_fast_pickscore.py:447-486): transformer + scheduler + VAE decoder."""
+reference, scripts/train_sd3_fast_pickscore.py:447-486): transformer + scheduler + VAE decoder, and optionally the VAE encoder
+(adv_grpo_amd/vae_encoder.py) for rollouts that start from reference images (diffusers_patch/sd3_img2img_with_logprob.py)."""
 import threading
 
 import torch
@@ -12,9 +13,10 @@ class SD3Pipeline:
     default_sample_size = 128
     vae_scale_factor = 8
 
-    def __init__(self, transformer, vae, device="cuda"):
+    def __init__(self, transformer, vae, device="cuda", vae_encoder=None):
         self.transformer = transformer
         self.vae = vae
+        self.vae_encoder = vae_encoder      # None: everything but the img2img entry points works as before
         self.device = torch.device(device)
         self.scheduler = FlowMatchEulerDiscreteScheduler(device=self.device)
         self._guidance_scale = 1.0

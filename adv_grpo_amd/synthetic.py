@@ -201,6 +201,40 @@ def vae_decoder_weights(cfg, seed=4321, fp16_checkpoint=False):
     return W
 
 
+def vae_encoder_weights(cfg, seed=8642, fp16_checkpoint=False):
+    """fp32 CPU weights keyed like diffusers AutoencoderKL.state_dict() (encoder.* only; SD3 has no quant_conv): conv_in, down blocks of
+    layers_per_block resnets with a Downsample2D convolution behind all but the last, mid block, conv_norm_out, conv_out to
+    2 * latent_channels moments (double_z).  fp16_checkpoint as vae_decoder_weights."""
+    g = _gen(seed)
+    W = {}
+    ch = list(cfg.block_out_channels)                     # 128, 256, 512, 512
+    conv_(W, "encoder.conv_in", ch[0], 3, 3, g)
+
+    def res(p, ci, co):
+        norm_(W, f"{p}.norm1", ci, g); conv_(W, f"{p}.conv1", co, ci, 3, g)
+        norm_(W, f"{p}.norm2", co, g); conv_(W, f"{p}.conv2", co, co, 3, g)
+        if ci != co:
+            conv_(W, f"{p}.conv_shortcut", co, ci, 1, g)
+    prev = ch[0]
+    for i, co in enumerate(ch):
+        for j in range(cfg.layers_per_block):
+            res(f"encoder.down_blocks.{i}.resnets.{j}", prev if j == 0 else co, co)
+        prev = co
+        if i < len(ch) - 1:
+            conv_(W, f"encoder.down_blocks.{i}.downsamplers.0.conv", co, co, 3, g)
+    res("encoder.mid_block.resnets.0", ch[-1], ch[-1])
+    a = "encoder.mid_block.attentions.0"
+    norm_(W, f"{a}.group_norm", ch[-1], g)
+    for n in ("to_q", "to_k", "to_v", "to_out.0"):
+        linear_(W, f"{a}.{n}", ch[-1], ch[-1], g)
+    res("encoder.mid_block.resnets.1", ch[-1], ch[-1])
+    norm_(W, "encoder.conv_norm_out", ch[-1], g)
+    conv_(W, "encoder.conv_out", 2 * cfg.latent_channels, ch[-1], 3, g)
+    if fp16_checkpoint:
+        W = {k: v.half().float() for k, v in W.items()}
+    return W
+
+
 def qwen_text_weights(cfg, seed=1357, dtype=None):
     """Weights keyed like transformers' Qwen2_5_VLTextModel.state_dict() (created on torch's default device: use on_device)."""
     g = _gen(seed)

@@ -35,6 +35,7 @@ class _PairRows:
 
 
 class AutoencoderKLDecoder:
+    _prefix = "decoder."             # the half of AutoencoderKL.state_dict() this class runs (vae_encoder.py: "encoder.")
     f16_single = False               # (class default: subclasses with their own constructor -- the Qwen-Image decoder -- have no such mode)
     def __init__(self, state_dict, cfg, device="cuda", mode="bf16x3", f16_weights=True, f16_single=False):
         """f16_weights (bf16x3 mode): run a 3x3 convolution whose weight tensor is EXACT in fp16 on the two-product f16x2 kernel
@@ -114,7 +115,7 @@ class AutoencoderKLDecoder:
         f32 = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()
         w = self.w
         for k, v in state_dict.items():
-            if not k.startswith("decoder."):
+            if not k.startswith(self._prefix):
                 continue
             if v.dim() == 4 and v.shape[-1] == 3:       # conv3x3 [Co,Ci,3,3] -> [Co, 9, Ci] -> split along Ci
                 v = f32(v)

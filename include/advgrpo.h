@@ -517,6 +517,36 @@ int64_t advgrpo_vae_decode_workspace_bytes(const advgrpo_vae_decoder_desc* decod
 int advgrpo_vae_decode(const advgrpo_vae_decoder_desc* decoder, const void* latents, int latents_dtype, float* image,
                        void* workspace /* 256-byte aligned */, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ the VAE encoder (csrc/vae_encode.hip, csrc/vae_encode_chain.cpp, conv_x3.hip)
+ * `pipe.vae.encode(img).latent_dist.sample() * scaling_factor` of image_to_latent (adv_grpo/diffusers_patch/sd3_pipeline_with_logprob_fast.py:
+ * 686-705) in the fp32-EQUIVALENT split-bf16 arithmetic of the decoder.
+ * conv3x3_s2_nhwc_x3: diffusers' Downsample2D(padding=0) = F.pad(x, (0, 1, 0, 1)) + 3x3 convolution of stride 2 without padding, the padding folded
+ *   into the tap addressing.  x3 [B, 2 Hout, 2 Wout, Cin3 = 3C] split rows (hi and lo thirds are read: advgrpo_split_bf16x3 order 2 or 0), w3
+ *   [Cout, 9 * Cin3] as advgrpo_conv3x3_nhwc_x3; Cin3 % 192 == 0, Cout >= 128; bias, y f32.
+ * image_to_nhwc_x3: image [B, 3, H, W] in [0, 1] (ADVGRPO_F32 / ADVGRPO_BF16) or uint8 [B, H, W, 3] (ADVGRPO_U8, divided by 255) ->
+ *   (x - 0.5) / 0.5 -> split rows [B, H, W, 3 Cpad] bf16, thirds [hi | unwritten | lo], channels 3 .. Cpad - 1 zero; Cpad % 8 == 0.
+ * vae_latent_tail, one launch: moments [B, h, w, 2 C] f32 NHWC (mean | logvar) -> z = mean + exp(0.5 clamp(logvar, -30, 20)) * eps, times
+ *   scaling_factor (shift_factor is NOT subtracted: image_to_latent does not), cast to z_dtype, NCHW [B, C, h, w] (z_out may be null when only the
+ *   mix is wanted).  mode 0: z = mean; 1: eps [B, C, h, w] f32 given; 2: eps from Philox, element i = value i % 4 of counter offset + i / 4 under
+ *   `seed` (the convention of advgrpo_randn).  mix_mode != 0 adds the forward noising of flux_to_sd3_denoise_random (:961-965) in bf16 arithmetic:
+ *   mix_out (bf16) = bf16(bf16(bf16(1 - s) * bf16(z)) + bf16(s * bf16(noise))) with s = bf16(sigma[0]) (device scalar); mix_mode 1: noise given
+ *   (f32 / bf16), 2: Philox under (mix_seed, mix_offset). */
+int advgrpo_conv3x3_s2_nhwc_x3(const void* x3, const void* w3, float* y, int B, int Hout, int Wout, int Cin3, int Cout, const float* bias,
+                               const void* zero_page, void* stream);
+int advgrpo_image_to_nhwc_x3(const void* image, int image_dtype, void* out3, int B, int H, int W, int Cpad, void* stream);
+int advgrpo_vae_latent_tail(const float* moments, int B, int C, int h, int w, int mode, const float* eps, uint64_t seed, uint64_t offset,
+                            float scaling_factor, void* z_out, int z_dtype, int mix_mode, const void* mix_noise, int mix_noise_dtype,
+                            uint64_t mix_seed, uint64_t mix_offset, const float* sigma, void* mix_out, void* stream);
+/* The whole encoder behind one entry, image -> moments [B, h / 8, w / 8, 2 latent_channels] f32 NHWC, bit-identical to the launches issued one by
+ * one (adv_grpo_amd/vae_encoder.py keeps that sequencing as the check).  The descriptor is advgrpo_vae_decoder_desc read the other way round:
+ * B, h, w = the IMAGE batch, height and width (multiples of 2^(n_up - 1), the latent pixel count a multiple of 64); n_up / resnets_per_up / up_resnets / upsamplers = the DOWN blocks,
+ * their resnets and the n_up - 1 Downsample2D convolutions in encoder order; conv_in.cin = 64 (the 3 image channels zero-padded), conv_out.cout =
+ * 2 * latent_channels; every convolution form 0 (split-bf16, three products), cout >= 128 except conv_out; scaling_factor / shift_factor /
+ * f16_single are not read. */
+int64_t advgrpo_vae_encode_workspace_bytes(const advgrpo_vae_decoder_desc* encoder);
+int advgrpo_vae_encode(const advgrpo_vae_decoder_desc* encoder, const void* images, int images_dtype, float* moments,
+                       void* workspace /* 256-byte aligned */, int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ a ViT encoder stack behind one entry (csrc/vit_encoder.cpp)
  * The pre-LN transformer encoder of the reward towers: transformers' CLIPEncoderLayer x n behind CLIPModel.get_image_features /
  * get_text_features (adv_grpo/pickscore_scorer.py:40-44, adv_grpo/pick_score_training.py:95-106; ViT-H/14: 32 layers, 16 heads x 80; text:

@@ -117,6 +117,17 @@ def main():
     dmax = (img - ref_img).abs().max().item()
     print(f"AutoencoderKL.decode + postprocess('pt'): max abs {dmax:.2e}")
     ok &= dmax < 1e-4
+    # ---------------------------------------------------------------- VAE encoder moments (image_to_latent, PF:703) vs tests/vae_encoder_reference.py
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import vae_encoder_reference as ver
+    We = {k: v.detach() for k, v in vae.state_dict().items() if k.startswith("encoder.")}
+    x = torch.rand(1, 3, 128, 128, device=dev) * 2 - 1
+    with torch.no_grad():
+        ref_m = vae.encode(x).latent_dist.parameters
+        got_m = ver.vae_encode_moments(We, vcfg, x)
+    emax = (got_m - ref_m).abs().max().item() / ref_m.abs().max().item()
+    print(f"AutoencoderKL.encode moments: normalised max {emax:.2e}")
+    ok &= emax < 1e-4
     # ---------------------------------------------------------------- Qwen-Image VAE decoder (BASELINE config 5; diffusers >= 0.35)
     try:
         from diffusers import AutoencoderKLQwenImage
