@@ -117,6 +117,8 @@ SIGNATURES = {
     "advgrpo_sde_step_workspace_bytes": (c_int64, [c_int, c_int64]),
     "advgrpo_sde_step": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, c_int, _P, c_uint64,
                                  c_uint64, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int64, _P]),
+    "advgrpo_sde_step_branch": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, c_int, _P, c_uint64,
+                                        c_uint64, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int64, _P]),
     "advgrpo_sde_step_bwd": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P, _P,
                                      _P, c_int, c_int64, _P]),
     "advgrpo_sde_step_bwd_kl": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P, _P, c_float,

@@ -6,6 +6,9 @@
 // is launch-latency bound at 512^2 (0.5 MB per sample), so it is shaped for few, wide
 // wavefronts: 16 B per lane per load, one block-level reduction, a tiny finalize launch.
 //
+// sde_step_branch_kernel is the fan-out form for the branch step of the shared-prefix rollouts: P rows in, P * G rows out, one read of the
+// inputs and one evaluation of the mean per up to 8 copies, the bits of sde_step_kernel on the materialised repeat.
+//
 // Built with -ffp-contract=off: every reference torch op is one f32 rounding here too, so
 // mean / next are bit-exact with the torch-CPU oracle; log_prob differs by summation order only.
 #include "common.hpp"
@@ -16,6 +19,7 @@ constexpr int SDE_THREADS = 256;
 constexpr int SDE_VEC = 8;                       // elements per lane per iteration
 constexpr int SDE_CHUNK = SDE_THREADS * SDE_VEC;  // 2048 elements per block iteration
 constexpr int SDE_MAX_BLOCKS = 64;               // per sample
+constexpr int SDE_BRANCH_COPIES = 8;             // sde_step_branch_kernel: copies of an input row per block
 
 __device__ inline void load8(const void* p, int dt, int64_t i, float o[8]) {
     if (dt == ADVGRPO_BF16) {
@@ -120,6 +124,77 @@ __global__ __launch_bounds__(SDE_THREADS) void sde_step_kernel(
     if (threadIdx.x == 0) {
         partial[b * gridDim.x + blockIdx.x] = tot;
         if (blockIdx.x == 0 && out_std) out_std[b] = c.std;
+    }
+}
+
+// Fan-out form of sde_step_kernel for the branch step of the shared-prefix rollouts (sd3_pipeline_with_logprob_fast.py:163, :385: the
+// latents are repeated G times and every copy takes its own epsilon).  v_u / v_t / x hold P rows; output row j = g * P + p (torch's
+// .repeat tiling) reads input row p.  A block owns the chunks sde_step_kernel's block (blockIdx.x, j) would own and runs the same f32
+// operations in the same order on them, so every output -- the block partials of log_prob included -- has the bits of sde_step_kernel on
+// the materialised repeat.  The 16 B of v_u, v_t and x per lane are loaded, and the mean is computed, once per chunk for up to
+// SDE_BRANCH_COPIES copies; the copies' running sums live in lane-private LDS slots (a runtime-indexed register array would go to scratch).
+__global__ __launch_bounds__(SDE_THREADS) void sde_step_branch_kernel(
+    const void* __restrict__ v_u, const void* __restrict__ v_t, int v_dt, float guidance,
+    const void* __restrict__ x, int x_dt, const float* __restrict__ sigma,
+    const float* __restrict__ sigma_prev, int sigma_stride, float sin_coeff, int mode,
+    const float* __restrict__ eps, uint64_t seed, uint64_t offset,
+    const void* __restrict__ prev, int prev_dt, float* __restrict__ out_next,
+    void* __restrict__ out_cast, int cast_dt, float* __restrict__ out_mean,
+    float* __restrict__ partial, float* __restrict__ out_std, int P, int G, int64_t n) {
+    __shared__ float red[SDE_THREADS / 64];
+    __shared__ float accs[SDE_BRANCH_COPIES][SDE_THREADS];
+    const int p = blockIdx.y;
+    const int g0 = blockIdx.z * SDE_BRANCH_COPIES;
+    const int ng = G - g0 < SDE_BRANCH_COPIES ? G - g0 : SDE_BRANCH_COPIES;
+    const SdeCoef c = sde_coef(sigma, sigma_prev, sigma_stride, p, sin_coeff);
+    const bool has_cfg = v_t != nullptr, bf = v_dt == ADVGRPO_BF16;
+    const int64_t in_base = (int64_t)p * n;
+    const Philox ph(seed);
+    for (int gg = 0; gg < ng; ++gg) accs[gg][threadIdx.x] = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * SDE_CHUNK + threadIdx.x * SDE_VEC; i < n;
+         i += (int64_t)gridDim.x * SDE_CHUNK) {
+        float vu[8], vt[8], xs[8], mean[8];
+        load8(v_u, v_dt, in_base + i, vu);
+        if (has_cfg) load8(v_t, v_dt, in_base + i, vt);
+        load8(x, x_dt, in_base + i, xs);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float v = cfg_v(vu[k], vt[k], has_cfg, bf, guidance);
+            const float x0 = xs[k] - c.sigma * v;              // :119
+            const float x1 = xs[k] + v * c.one_m_sigma;         // :120
+            mean[k] = x0 * c.one_m_sigma_prev + x1 * c.sq;     // :121
+        }
+        for (int gg = 0; gg < ng; ++gg) {
+            const int64_t o = ((int64_t)(g0 + gg) * P + p) * n + i;   // element (j, i) of the P * G-row outputs
+            float e[8], nxt[8];
+            if (mode == ADVGRPO_SDE_EPS) {
+                load8(eps, ADVGRPO_F32, o, e);
+            } else if (mode == ADVGRPO_SDE_PHILOX) {
+                philox_normal4(ph, offset + (uint64_t)(o >> 2), e);
+                philox_normal4(ph, offset + (uint64_t)(o >> 2) + 1, e + 4);
+            } else {
+                load8(prev, prev_dt, o, e);  // e holds prev_sample
+            }
+            float acc = accs[gg][threadIdx.x];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                nxt[k] = (mode == ADVGRPO_SDE_REPLAY) ? e[k] : mean[k] + c.std * e[k];  // :131
+                const float d = nxt[k] - mean[k];
+                acc += d * d;                                       // :134 (negated at finalize)
+            }
+            accs[gg][threadIdx.x] = acc;
+            if (out_next && mode != ADVGRPO_SDE_REPLAY) store8(out_next, ADVGRPO_F32, o, nxt);
+            if (out_cast && mode != ADVGRPO_SDE_REPLAY) store8(out_cast, cast_dt, o, nxt);
+            if (out_mean) store8(out_mean, ADVGRPO_F32, o, mean);
+        }
+    }
+    for (int gg = 0; gg < ng; ++gg) {
+        const float tot = block_sum<SDE_THREADS / 64>(accs[gg][threadIdx.x], red);
+        if (threadIdx.x == 0) {
+            const int64_t j = (int64_t)(g0 + gg) * P + p;
+            partial[j * gridDim.x + blockIdx.x] = tot;
+            if (blockIdx.x == 0 && out_std) out_std[j] = c.std;
+        }
     }
 }
 
@@ -240,6 +315,32 @@ extern "C" int advgrpo_sde_step(const void* v_uncond, const void* v_text, int v_
                        v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride, sin_coeff, mode, eps,
                        seed, offset, prev_sample, prev_dtype, out_next_f32, out_next_cast, out_cast_dtype, out_mean,
                        (float*)workspace, out_std, n);
+    ADVGRPO_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sde_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream),
+                       (const float*)workspace, nb, n, out_log_prob, B);
+    ADVGRPO_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int advgrpo_sde_step_branch(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                       const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                       int sigma_stride, float sin_coeff, int mode, const float* eps, uint64_t seed,
+                                       uint64_t offset, const void* prev_sample, int prev_dtype, float* out_next_f32,
+                                       void* out_next_cast, int out_cast_dtype, float* out_mean, float* out_log_prob,
+                                       float* out_std, void* workspace, int P, int G, int64_t n, void* stream) {
+    ADVGRPO_CHECK(P > 0 && G > 0, "sde_step_branch: need P>0 and G>0 (P=%d G=%d)", P, G);
+    if (check_common(v_dtype, x_dtype, P, n)) return -1;
+    const int gz = (G + SDE_BRANCH_COPIES - 1) / SDE_BRANCH_COPIES;
+    ADVGRPO_CHECK(P <= 65535 && gz <= 65535 && (int64_t)P * G <= INT32_MAX, "sde_step_branch: P=%d G=%d too large", P, G);
+    ADVGRPO_CHECK(v_uncond && x && sigma && sigma_prev && out_log_prob && workspace, "sde_step_branch: null argument");
+    ADVGRPO_CHECK(mode >= 0 && mode <= 2, "sde_step_branch: bad mode %d", mode);
+    ADVGRPO_CHECK(mode != ADVGRPO_SDE_EPS || eps, "sde_step_branch: mode EPS needs eps");
+    ADVGRPO_CHECK(mode != ADVGRPO_SDE_REPLAY || prev_sample, "sde_step_branch: mode REPLAY needs prev_sample");
+    const int nb = sde_blocks(n), B = P * G;
+    hipLaunchKernelGGL(sde_step_branch_kernel, dim3(nb, P, gz), dim3(SDE_THREADS), 0, as_stream(stream), v_uncond, v_text,
+                       v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride, sin_coeff, mode, eps,
+                       seed, offset, prev_sample, prev_dtype, out_next_f32, out_next_cast, out_cast_dtype, out_mean,
+                       (float*)workspace, out_std, P, G, n);
     ADVGRPO_LAUNCH_CHECK();
     hipLaunchKernelGGL(sde_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream),
                        (const float*)workspace, nb, n, out_log_prob, B);

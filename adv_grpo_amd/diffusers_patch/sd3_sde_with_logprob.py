@@ -26,20 +26,26 @@ def _sigma_tables(scheduler, timestep, B, device):
 
 def sde_step_cfg(scheduler, v_uncond, v_text, guidance_scale, timestep, sample, noise_level=0.7,
                  prev_sample=None, noise=None, seed=None, offset=0, out_dtype=None, want_mean=True,
-                 step_index=None, sigmas=None):
+                 step_index=None, sigmas=None, copies=None):
     """Returns (prev_sample_f32_or_None, prev_sample_cast_or_None, log_prob, prev_sample_mean_or_None, std_dev_t).
 
     v_text=None => no CFG.  Exactly one of prev_sample (replay), noise (injected epsilon) or seed
-    (in-kernel Philox) selects the mode."""
+    (in-kernel Philox) selects the mode.
+
+    copies=G: the fan-out step of the branching rollouts (advgrpo_sde_step_branch).  v_uncond / v_text / sample hold P rows,
+    noise / prev_sample and every output P * G rows; output row j continues input row j % P (``sample.repeat(G, 1, 1, 1)``)
+    with its own epsilon -- the bits of this function on the repeated inputs, without the repeat and with one read of them."""
     lib = _lib.load()
-    B = sample.shape[0]
+    P = sample.shape[0]
+    B = P if copies is None else P * int(copies)
+    out_shape = (B, *sample.shape[1:])
     n = sample[0].numel()
     dev = sample.device
     if step_index is not None:
         tab = scheduler.sigmas if sigmas is None else sigmas       # `sigmas`: the caller's rollout-local table
         sig, sigp, stride = tab[step_index:step_index + 1], tab[step_index + 1:step_index + 2], 0
     else:
-        sig, sigp, stride = _sigma_tables(scheduler, timestep, B, dev)
+        sig, sigp, stride = _sigma_tables(scheduler, timestep, P, dev)
     v_uncond = v_uncond.contiguous()
     v_text = v_text.contiguous() if v_text is not None else None
     sample = sample.contiguous()
@@ -52,22 +58,26 @@ def sde_step_cfg(scheduler, v_uncond, v_text, guidance_scale, timestep, sample, 
             raise ValueError("sampling mode needs `noise` or `seed`")
         mode = _lib.SDE_PHILOX
     replay = mode == _lib.SDE_REPLAY
-    nxt = None if replay else torch.empty(sample.shape, dtype=torch.float32, device=dev)
+    for name, t in (("noise", noise if mode == _lib.SDE_EPS else None), ("prev_sample", prev_sample)):
+        if copies is not None and t is not None and tuple(t.shape) != out_shape:
+            raise ValueError(f"sde_step_cfg(copies={copies}): {name} must have the output's shape {out_shape}, got {tuple(t.shape)}")
+    nxt = None if replay else torch.empty(out_shape, dtype=torch.float32, device=dev)
     cast = None
     if not replay and out_dtype is not None and out_dtype != torch.float32:
-        cast = torch.empty(sample.shape, dtype=out_dtype, device=dev)
-    mean = torch.empty(sample.shape, dtype=torch.float32, device=dev) if want_mean else None
+        cast = torch.empty(out_shape, dtype=out_dtype, device=dev)
+    mean = torch.empty(out_shape, dtype=torch.float32, device=dev) if want_mean else None
     lp = torch.empty(B, dtype=torch.float32, device=dev)
     std = torch.empty(B, dtype=torch.float32, device=dev)
     ws = torch.empty(max(1, lib.advgrpo_sde_step_workspace_bytes(B, n) // 4), dtype=torch.float32, device=dev)
-    _lib.check(lib.advgrpo_sde_step(
+    entry = lib.advgrpo_sde_step if copies is None else lib.advgrpo_sde_step_branch
+    _lib.check(entry(
         _lib.ptr(v_uncond), _lib.ptr(v_text), _lib.dtype_code(v_uncond.dtype), float(guidance_scale),
         _lib.ptr(sample), _lib.dtype_code(sample.dtype), _lib.ptr(sig), _lib.ptr(sigp), stride,
         float(math.sin(noise_level * math.pi / 2)), mode, _lib.ptr(noise) if mode == _lib.SDE_EPS else None,
         int(seed or 0), int(offset), _lib.ptr(prev_sample) if replay else None,
         _lib.dtype_code(prev_sample.dtype) if replay else 0, _lib.ptr(nxt), _lib.ptr(cast),
         _lib.dtype_code(cast.dtype) if cast is not None else 0, _lib.ptr(mean), _lib.ptr(lp), _lib.ptr(std),
-        _lib.ptr(ws), B, n, _lib.stream_ptr()))
+        _lib.ptr(ws), *((B,) if copies is None else (P, int(copies))), n, _lib.stream_ptr()))
     return nxt, cast, lp, mean, std.view(-1, *([1] * (sample.dim() - 1)))
 
 

@@ -21,7 +21,7 @@ from . import distributed as D
 from . import g_step, ops, rewards, stat_tracking
 from .d_step import train_dino
 from .d_step_pickscore import ClipLastLayerTrainable, ClipLayersTrainable, train_pickscore
-from .diffusers_patch.sd3_pipeline_with_logprob_fast import pipeline_with_logprob_random
+from .diffusers_patch.sd3_pipeline_with_logprob_fast import pipeline_with_logprob_new, pipeline_with_logprob_random
 from .sampler import DistributedKRepeatSampler
 
 
@@ -339,8 +339,12 @@ class Trainer:
             ref = self.data.reference_images(idx, G) if self.needs_reference else None     # TP:773-801
             return idx, pe, ppe, ref, self.data.clip_ids(idx, G)
 
+        # opt-in `sample.branch_rollout`: the reference's shared-prefix rollout (PF:234-448) -- one latent through the noise-free prefix, repeated G
+        # times at the first SDE step.  The G samples of a group then share their initial noise; the sample dict keeps its keys and shapes.
+        rollout_fn = pipeline_with_logprob_new if c.sample.get("branch_rollout", False) else pipeline_with_logprob_random
+
         def rollout(i, idx, pe, ppe, ref, prompts):
-            images, lats, lps, tss = pipeline_with_logprob_random(
+            images, lats, lps, tss = rollout_fn(
                 self.pipe, prompt_embeds=pe, pooled_prompt_embeds=ppe, negative_prompt_embeds=neg_pe,
                 negative_pooled_prompt_embeds=neg_ppe, num_inference_steps=c.sample.num_steps,
                 guidance_scale=c.sample.guidance_scale, output_type="pt", height=c.resolution, width=c.resolution,

@@ -69,6 +69,23 @@ int advgrpo_sde_step(const void* v_uncond, const void* v_text, int v_dtype, floa
                      float* out_mean, float* out_log_prob, float* out_std,
                      void* workspace, int B, int64_t n, void* stream);
 
+/* Fan-out form for the branch step of the shared-prefix rollouts pipeline_with_logprob(_new)
+ * (sd3_pipeline_with_logprob_fast.py:163, :385): the transformer ran on P un-repeated rows and every row
+ * continues as G copies, each with its own epsilon.  v_uncond / v_text / x: [P, n].  eps (EPS), prev_sample
+ * (REPLAY), out_next_f32, out_next_cast, out_mean: [P*G, n]; out_log_prob, out_std: [P*G].  Output row j reads
+ * input row j % P (torch's .repeat tiling); sigma / sigma_prev: element (j % P)*sigma_stride.  In PHILOX mode
+ * element (j, k) draws the counter advgrpo_sde_step uses for element (j, k) of a P*G-row batch.  Every output
+ * has the bits of advgrpo_sde_step(B = P*G) on the materialised repeat, log_prob included.
+ * workspace: >= advgrpo_sde_step_workspace_bytes(P*G, n) bytes. */
+int advgrpo_sde_step_branch(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                            const void* x, int x_dtype,
+                            const float* sigma, const float* sigma_prev, int sigma_stride, float sin_coeff,
+                            int mode, const float* eps, uint64_t seed, uint64_t offset,
+                            const void* prev_sample, int prev_dtype,
+                            float* out_next_f32, void* out_next_cast, int out_cast_dtype,
+                            float* out_mean, float* out_log_prob, float* out_std,
+                            void* workspace, int P, int G, int64_t n, void* stream);
+
 /* Backward of the replay-mode step w.r.t. the two CFG halves of the transformer output
  * (autograd of train_sd3_fast_pickscore.py:242-265 as reached from loss.backward(), :1165):
  *   g_v = grad_log_prob[b] * 2*(prev-mean)/n * ((1-sigma)*sqrt(sigma_prev^2-std^2) - sigma*(1-sigma_prev))

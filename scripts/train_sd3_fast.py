@@ -40,7 +40,7 @@ def parse_reward_fn(text):
     return out
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True)
     ap.add_argument("--reward-fn", type=parse_reward_fn, default=None, metavar="NAME=W[,NAME=W]",
@@ -57,6 +57,10 @@ def main():
                     help="override sample.groups_in_flight (prompt groups rolled out concurrently on separate HIP streams)")
     ap.add_argument("--cfg-streams", action="store_true",
                     help="sample.cfg_two_streams: the unconditional and conditional halves of every rollout forward on two HIP streams (same samples)")
+    ap.add_argument("--branch-rollout", action="store_true",
+                    help="sample.branch_rollout: roll a prompt group out with the reference's pipeline_with_logprob_new -- one latent through the "
+                         "noise-free prefix, repeated at the first SDE step.  The images of a group then share their initial noise and prefix: "
+                         "their spread comes from the SDE window alone")
     ap.add_argument("--lora-mode", default="merged", choices=["merged", "side"],
                     help="merged: LoRA folded into the bf16 weights (default); side: PEFT's side-path arithmetic (TP:490-511)")
     ap.add_argument("--no-train-d", action="store_true", help="keep the discriminator frozen: every epoch is a G-step epoch")
@@ -80,7 +84,11 @@ def main():
                          "clipscore rewards")
     ap.add_argument("--aesthetic-head", default=None, metavar="FILE",
                     help="the aesthetic predictor's sac+logos+ava1-l14-linearMSE.pth (needed by the aesthetic reward)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     from adv_grpo_amd.config.experiments import parse_config_flag
     cfg = parse_config_flag(args.config, gpu_number=world)
@@ -121,6 +129,8 @@ def main():
         cfg.sample.groups_in_flight = args.groups_in_flight
     if args.cfg_streams:
         cfg.sample.cfg_two_streams = True
+    if args.branch_rollout:
+        cfg.sample.branch_rollout = True
     if args.no_train_d:
         cfg.train_d = False
     if args.batches:
