@@ -16,12 +16,17 @@ in-kernel Philox stream unless injected.  The latents keep the reference's conve
 Keyword-only hooks for parity tests, defaulting to the reference's behaviour: ``target_idx`` (skips the randint), ``encode_noise`` (the VAE
 sampling epsilon), ``mix_noise`` (the forward-noising draw), ``noises`` (per denoise step, indexed from the start step), ``seed`` and
 ``output_type="latent"``.
+
+The denoise loop is its own (start offset, Philox offsets, fixed noise level and recording rule differ from ``_rollout.rollout``) over that
+module's helpers.  ``pipe.cfg_two_streams`` (default false) is honoured as in the other rollouts: the two halves of the CFG batch as two
+forwards on two HIP streams, with the same bits as one forward of twice the batch.
 """
 import random
 
 import torch
 
 from .. import _lib
+from ._rollout import NEED_EMBEDS, cfg_embeddings, hoist, output, velocity
 from .sd3_sde_with_logprob import sde_step_cfg
 
 NO_ENCODER = ("this SD3Pipeline was built without a VAE encoder: pass vae_encoder=AutoencoderKLEncoder(...) "
@@ -98,17 +103,15 @@ def flux_to_sd3_denoise_random(self, prompt=None, prompt_2=None, prompt_3=None, 
                                noises=None, seed=None):
     enc = _encoder(self)
     if prompt_embeds is None:
-        raise ValueError("prompt strings need text encoders, which are outside the accelerated path "
-                         "(SURVEY.md 8a2 / f3): pass prompt_embeds / pooled_prompt_embeds")
+        raise ValueError(NEED_EMBEDS)
     if flux_images is None:
         raise ValueError("flux_to_sd3_denoise_random: flux_images (PIL images or a [B,3,H,W] tensor in [0,1]) is required")
     self._guidance_scale = guidance_scale
     device = self._execution_device if device == "cuda" else torch.device(device)
-    do_cfg = guidance_scale > 1
     images = _as_device_images(flux_images, device)
     sched = self.scheduler
     sched.set_timesteps(num_inference_steps, device=device)                    # PF:948-949
-    timesteps, sigma_table = sched.timesteps, sched.sigmas                     # rollout-local view (see pipeline_with_logprob_random)
+    timesteps, sigma_table = sched.timesteps, sched.sigmas                     # rollout-local view (see _rollout.rollout)
     ts_host = [float(v) for v in sched._timesteps_host] if hasattr(sched, "_timesteps_host") else timesteps.tolist()
     if target_idx is None:
         target_idx = draw_target_idx()                                         # PF:958
@@ -134,30 +137,17 @@ def flux_to_sd3_denoise_random(self, prompt=None, prompt_2=None, prompt_3=None, 
         latents = (1.0 - sg) * z + sg * mix_noise.to(device=device, dtype=torch.bfloat16)
     B = latents.shape[0]
     dtype = latents.dtype
-    pe = prompt_embeds.to(device).repeat(B, 1, 1)                              # PF:1009-1012
-    ppe = pooled_prompt_embeds.to(device).repeat(B, 1)
-    if do_cfg:
-        npe = negative_prompt_embeds.to(device).repeat(B, 1, 1)
-        nppe = negative_pooled_prompt_embeds.to(device).repeat(B, 1)
-        tem_pe, tem_ppe = torch.cat([npe, pe], dim=0), torch.cat([nppe, ppe], dim=0)
-    else:
-        tem_pe, tem_ppe = pe, ppe
+    tem_pe, tem_ppe, do_cfg = cfg_embeddings(prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds,
+                                             device, guidance_scale, repeat=B)                       # PF:1009-1012
     run = timesteps[start:]                                                    # PF:1026
     all_latents, all_log_probs, all_timesteps = [], [], []
     ctr = (latents.numel() + 3) // 4 + 1      # Philox counters: [0, ctr) the VAE sampling draw, [ctr, 2 ctr) the mix, then one range per step
-    pre = getattr(self.transformer, "precompute_mods", None)
-    mods_all = pre(run, tem_ppe) if pre is not None else None
-    emb = getattr(self.transformer, "embed_context", None)
-    ctx_rows = emb(tem_pe) if emb is not None else None
+    mods_all, ctx_rows = hoist(self.transformer, run, tem_pe, tem_ppe)
     for k in range(len(run)):
         t = run[k]
         if k == 0:
             all_latents.append(latents)                                        # PF:1032-1033
-        inp = torch.cat([latents] * 2) if do_cfg else latents
-        v = self.transformer(hidden_states=inp, timestep=t.expand(inp.shape[0]), encoder_hidden_states=tem_pe, pooled_projections=tem_ppe,
-                             return_dict=False, **({} if mods_all is None else {"mods": mods_all[k]}),
-                             **({} if ctx_rows is None else {"context": ctx_rows}))[0]
-        vu, vt = (v[:B], v[B:]) if do_cfg else (v, None)
+        vu, vt = velocity(self, latents, t, B, tem_pe, tem_ppe, None if mods_all is None else mods_all[k], ctx_rows, do_cfg)
         _, cast, log_prob, _, _ = sde_step_cfg(sched, vu, vt, guidance_scale, None, latents, noise_level,       # PF:1055-1063
                                                noise=None if noises is None else noises[k], seed=seed, offset=(2 + k) * ctr,
                                                out_dtype=dtype, want_mean=False, step_index=start + k, sigmas=sigma_table)
@@ -166,11 +156,4 @@ def flux_to_sd3_denoise_random(self, prompt=None, prompt_2=None, prompt_3=None, 
             all_latents.append(latents)
             all_log_probs.append(log_prob)
             all_timesteps.append(t.repeat(B))
-    if output_type == "latent":
-        return latents, all_latents, all_log_probs, all_timesteps
-    image = self.vae.decode_to_image(latents)                                  # PF:1074-1079
-    if output_type == "pil":
-        from PIL import Image
-        arr = (image.clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
-        image = [Image.fromarray(a) for a in arr]
-    return image, all_latents, all_log_probs, all_timesteps
+    return output(self, latents, output_type, pil=True), all_latents, all_log_probs, all_timesteps      # PF:1074-1079

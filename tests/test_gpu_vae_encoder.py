@@ -335,11 +335,9 @@ def test_img2img_matches_reference_trajectory():
     assert random.getstate() == state and torch.equal(image2, image) and all(torch.equal(a, b) for a, b in zip(lats, lats2))
 
 
-def test_img2img_end_to_end_on_own_models():
-    """encoder -> noise -> denoise -> decode at 128 x 128 with a 2-block MMDiT: runs, finite, repeatable for a fixed seed; with noise_level 0,
-    the start at the LAST step (sigma of the mix and of the one denoise step small) the image stays close to decode(encode(x))."""
+def _own_models():
+    """-> (pipe, encoder, decoder, images, kwargs): a 2-block MMDiT, the VAE encoder and decoder on synthetic weights, two 128 x 128 images"""
     from adv_grpo_amd import synthetic
-    from adv_grpo_amd.diffusers_patch import sd3_img2img_with_logprob as I2I
     from adv_grpo_amd.mmdit import SD3Transformer2DModel
     from adv_grpo_amd.model_configs import MMDiTConfig
     from adv_grpo_amd.pipeline import SD3Pipeline
@@ -356,6 +354,14 @@ def test_img2img_end_to_end_on_own_models():
     img = _images(2, 128, 128, 8).cuda()
     kw = dict(flux_images=img, num_inference_steps=20, guidance_scale=4.5, prompt_embeds=pe, negative_prompt_embeds=npe,
               pooled_prompt_embeds=ppe, negative_pooled_prompt_embeds=nppe)
+    return pipe, enc, dec, img, kw
+
+
+def test_img2img_end_to_end_on_own_models():
+    """encoder -> noise -> denoise -> decode at 128 x 128 with a 2-block MMDiT: runs, finite, repeatable for a fixed seed; with noise_level 0,
+    the start at the LAST step (sigma of the mix and of the one denoise step small) the image stays close to decode(encode(x))."""
+    from adv_grpo_amd.diffusers_patch import sd3_img2img_with_logprob as I2I
+    pipe, enc, dec, img, kw = _own_models()
     random.seed(1)
     a = I2I.flux_to_sd3_denoise_random(pipe, seed=11, **kw)
     random.seed(1)
@@ -371,3 +377,22 @@ def test_img2img_end_to_end_on_own_models():
     err = (image - want).abs().mean().item()
     print("img2img at the last step vs decode(encode(x)): mean abs", err, "image std", want.std().item())
     assert err < 0.05 * max(want.std().item(), 1e-3) + 0.02
+
+
+def test_img2img_cfg_halves_on_two_streams_give_the_same_rollout():
+    """pipe.cfg_two_streams under flux_to_sd3_denoise_random: the two halves of the CFG batch as two forwards on two HIP streams give the image,
+    the recorded latents and the log-probs of the one forward of twice the batch, bit for bit (every row of every kernel of the transformer
+    is independent of the other rows; tests/test_gpu_rollout.py has the same statement for pipeline_with_logprob_random)."""
+    from adv_grpo_amd.diffusers_patch import sd3_img2img_with_logprob as I2I
+    pipe, _, _, _, kw = _own_models()
+    a = I2I.flux_to_sd3_denoise_random(pipe, seed=11, target_idx=7, **kw)
+    pipe.cfg_two_streams = True
+    try:
+        b = I2I.flux_to_sd3_denoise_random(pipe, seed=11, target_idx=7, **kw)
+        torch.cuda.synchronize()
+        assert "_cfg_sides" in pipe.__dict__                  # the second call did go through the two-stream schedule
+    finally:
+        pipe.cfg_two_streams = False
+    assert len(a[1]) == 3 and len(a[2]) == 2 and torch.isfinite(a[0]).all()
+    assert torch.equal(a[0], b[0])
+    assert all(torch.equal(x, y) for x, y in zip(a[1], b[1])) and all(torch.equal(x, y) for x, y in zip(a[2], b[2]))
