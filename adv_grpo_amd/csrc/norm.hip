@@ -543,6 +543,7 @@ extern "C" int advgrpo_timestep_embedding(const float* t, void* out, int B, int 
 
 extern "C" int advgrpo_unary(const void* x, const void* x2, void* y, int64_t n, int act, void* stream) {
     ADVGRPO_CHECK(x && y && n > 0 && n % 8 == 0, "unary: need n %% 8 == 0");
+    ADVGRPO_CHECK(act == 0 || act == 3, "unary: activation code %d not supported (0 none, 3 silu; the GEMM epilogues own the others)", act);
     int64_t blocks = (n / 8 + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(unary_kernel, dim3((int)blocks), dim3(256), 0, as_stream(stream), (const bf16_t*)x,

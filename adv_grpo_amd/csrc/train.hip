@@ -343,7 +343,8 @@ extern "C" int advgrpo_layernorm_mod_bwd(const void* x, int64_t ldx, const void*
                                          const void* scale0, const void* scale1, int64_t mod_stride, int rows_per_batch,
                                          const void* dres, void* dx, int64_t lddx, int M, int D, float eps, void* stream) {
     ADVGRPO_CHECK(x && dy0 && dx, "layernorm_mod_bwd: null pointer");
-    ADVGRPO_CHECK(M > 0 && D % 8 == 0 && D <= 4096, "layernorm_mod_bwd: need D %% 8 == 0, D <= 4096 (D=%d)", D);
+    ADVGRPO_CHECK(M > 0 && D > 0 && D % 8 == 0 && D <= 4096, "layernorm_mod_bwd: need D > 0, D %% 8 == 0, D <= 4096 (D=%d)", D);
+    ADVGRPO_CHECK(ldx % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0 && mod_stride % 8 == 0, "layernorm_mod_bwd: pitches must be multiples of 8");
     ADVGRPO_CHECK(!dy1 || scale1, "layernorm_mod_bwd: dy1 needs scale1");
     LnBwdParams p{(const bf16_t*)x, ldx, (const bf16_t*)dy0, (const bf16_t*)dy1, lddy, (const bf16_t*)scale0,
                   (const bf16_t*)scale1, mod_stride, rows_per_batch, (const bf16_t*)dres, (bf16_t*)dx, lddx, M, D, eps,
@@ -357,7 +358,8 @@ extern "C" int advgrpo_layernorm_mod_bwd_gated(const void* x, int64_t ldx, const
                                                const void* gate_a, void* gout_a, const void* gate_b, void* gout_b,
                                                int64_t gate_stride, void* stream) {
     ADVGRPO_CHECK(x && dy0 && dx, "layernorm_mod_bwd_gated: null pointer");
-    ADVGRPO_CHECK(M > 0 && D % 8 == 0 && D <= 4096, "layernorm_mod_bwd_gated: need D %% 8 == 0, D <= 4096 (D=%d)", D);
+    ADVGRPO_CHECK(M > 0 && D > 0 && D % 8 == 0 && D <= 4096, "layernorm_mod_bwd_gated: need D > 0, D %% 8 == 0, D <= 4096 (D=%d)", D);
+    ADVGRPO_CHECK(ldx % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0 && mod_stride % 8 == 0 && gate_stride % 8 == 0, "layernorm_mod_bwd_gated: pitches must be multiples of 8");
     ADVGRPO_CHECK(!dy1 || scale1, "layernorm_mod_bwd_gated: dy1 needs scale1");
     ADVGRPO_CHECK(gate_a && gout_a && rows_per_batch > 0, "layernorm_mod_bwd_gated: the first gate, its output and rows_per_batch are required");
     ADVGRPO_CHECK(!gate_b == !gout_b, "layernorm_mod_bwd_gated: the second gate and its output come together");
@@ -397,7 +399,8 @@ extern "C" int advgrpo_qk_norm_rope_bwd(void* dy, int64_t lddy, const void* y, i
 
 extern "C" int advgrpo_gate_mul(const void* x, const void* gate, void* y, int M, int D, int rows_per_batch,
                                 int64_t gate_stride, void* stream) {
-    ADVGRPO_CHECK(x && gate && y && M > 0 && D % 8 == 0 && rows_per_batch > 0, "gate_mul: bad argument");
+    ADVGRPO_CHECK(x && gate && y && M > 0 && D > 0 && D % 8 == 0 && rows_per_batch > 0, "gate_mul: bad argument (need D > 0, D %% 8 == 0; D=%d)", D);
+    ADVGRPO_CHECK(gate_stride % 8 == 0, "gate_mul: the gate pitch must be a multiple of 8");
     const int64_t total8 = (int64_t)M * (D / 8);
     hipLaunchKernelGGL(gate_mul_kernel, dim3(grid_for(total8, 256)), dim3(256), 0, as_stream(stream), (const bf16_t*)x,
                        (const bf16_t*)gate, (bf16_t*)y, total8, D / 8, rows_per_batch, gate_stride);

@@ -219,7 +219,7 @@ int advgrpo_rope_half(void* buf, int64_t ld, int rows, int T, int col0, int nhea
 int advgrpo_softmax_rows_causal(const float* sc, void* p16, int64_t rows, int n, void* stream);
 /* diffusers Timesteps(256, flip_sin_to_cos=True, downscale_freq_shift=0): t f32 [B] -> bf16 [B, dim]. */
 int advgrpo_timestep_embedding(const float* t, void* out, int B, int dim, void* stream);
-/* y = act(x [+ x2]) on bf16, n % 8 == 0 (act 0 none, 3 SiLU). */
+/* y = act(x [+ x2]) on bf16, n % 8 == 0; act 0 (none) or 3 (SiLU) -- any other activation code is refused (they live in the GEMM epilogues). */
 int advgrpo_unary(const void* x, const void* x2, void* y, int64_t n, int act, void* stream);
 /* [B,C,H,W] latents <-> 2x2 patch token rows (PatchEmbed conv k2 s2 as im2col; proj_out unpatchify). */
 int advgrpo_patchify(const void* x, int x_dtype, void* out, int B, int C, int H, int W, void* stream);
