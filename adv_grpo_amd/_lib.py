@@ -123,6 +123,15 @@ SIGNATURES = {
                                      _P, c_int, c_int64, _P]),
     "advgrpo_sde_step_bwd_kl": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P, _P, c_float,
                                         _P, _P, _P, _P, c_int, c_int64, _P]),
+    # the Flow-SDE siblings: the arguments of their Flow-CPS namesakes with `const float* sigma_max` after the noise level
+    "advgrpo_flow_sde_step": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P, c_uint64,
+                                      c_uint64, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int64, _P]),
+    "advgrpo_flow_sde_step_branch": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P, c_uint64,
+                                             c_uint64, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int64, _P]),
+    "advgrpo_flow_sde_step_bwd": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, _P, c_int, _P, _P,
+                                          _P, c_int, c_int64, _P]),
+    "advgrpo_flow_sde_step_bwd_kl": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, _P, c_int, _P, _P, c_float,
+                                             _P, _P, _P, _P, c_int, c_int64, _P]),
     "advgrpo_group_advantage": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, _P]),
     "advgrpo_group_advantage_stats": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, _P, _P]),
     "advgrpo_grpo_loss": (c_int, [_P, _P, _P, c_int, c_float, c_float, _P, _P, _P]),

@@ -1,4 +1,4 @@
-// sde_step.hip -- fused CFG combine + Flow-CPS SDE step + per-sample Gaussian log-prob (gfx950).
+// sde_step.hip -- fused CFG combine + Flow-CPS or Flow-SDE step + per-sample Gaussian log-prob (gfx950).
 //
 // Replaces sd3_pipeline_with_logprob_fast.py:640-655 and sd3_sde_with_logprob.py:77-139 of the
 // reference (six torch elementwise kernels, a randn, a .mean and two host syncs per step) with
@@ -9,8 +9,13 @@
 // sde_step_branch_kernel is the fan-out form for the branch step of the shared-prefix rollouts: P rows in, P * G rows out, one read of the
 // inputs and one evaluation of the mean per up to 8 copies, the bits of sde_step_kernel on the materialised repeat.
 //
+// Every kernel is a template over the step's arithmetic: CpsStep (Flow-CPS, SDE:117-134) or FlowStep (the original Flow-GRPO SDE with its
+// full Gaussian log-density, SDE:44-67).  Loads, CFG combine, epsilon, stores and reductions are the same code for both.
+//
 // Built with -ffp-contract=off: every reference torch op is one f32 rounding here too, so
 // mean / next are bit-exact with the torch-CPU oracle; log_prob differs by summation order only.
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace advgrpo {
@@ -77,17 +82,59 @@ __device__ inline float cfg_v(float vu, float vt, bool has_cfg, bool bf, float g
     return r;
 }
 
+// Flow-CPS (SDE:117-134): x' = mean + std * eps, log_prob = mean_i -(x' - mean)^2
+struct CpsStep {
+    SdeCoef c;
+    __device__ CpsStep(const float* sigma, const float* sigma_prev, int stride, int b, float sin_coeff, const float*)
+        : c(sde_coef(sigma, sigma_prev, stride, b, sin_coeff)) {}
+    __device__ float mean(float x, float v) const {
+        const float x0 = x - c.sigma * v;                     // :119
+        const float x1 = x + v * c.one_m_sigma;                // :120
+        return x0 * c.one_m_sigma_prev + x1 * c.sq;            // :121
+    }
+    __device__ float noise() const { return c.std; }           // :131 the factor of eps
+    __device__ float std() const { return c.std; }
+    // d mean / d v, and grad_log_prob * d log_prob / d mean = grad_log_prob * 2 (prev - mean) / n
+    __device__ float dmu_dv() const { return c.one_m_sigma * c.sq - c.sigma * c.one_m_sigma_prev; }
+    __device__ float lp_scale(float glp, int64_t n) const { return glp * 2.0f / (float)n * dmu_dv(); }
+};
+
+// Flow-SDE (SDE:44-67), every scalar in f32 in the reference's operation order:
+//   s = sqrt(sigma / (1 - (sigma == 1 ? sigma_max : sigma))) * noise_level ; dt = sigma_prev - sigma ; w = s * sqrt(-dt)
+//   mean = x * (1 + s^2 / (2 sigma) * dt) + v * (1 + s^2 (1 - sigma) / (2 sigma)) * dt ; x' = mean + w * eps
+//   log_prob = mean_i( -(x' - mean)^2 / (2 w^2) ) - log w - log sqrt(2 pi)         (flow_sde_finalize_kernel)
+struct FlowStep {
+    float cx, cv, dt, s, w;
+    __device__ FlowStep(const float* sigma, const float* sigma_prev, int stride, int b, float noise_level,
+                        const float* sigma_max) {
+        const float sg = sigma[(int64_t)b * stride], sp = sigma_prev[(int64_t)b * stride];
+        dt = sp - sg;                                                      // :47
+        s = sqrtf(sg / (1.0f - (sg == 1.0f ? sigma_max[0] : sg))) * noise_level;   // :49
+        const float s2 = s * s, two_sigma = 2.0f * sg;
+        cx = 1.0f + s2 / two_sigma * dt;                                   // :53, the factor of x
+        cv = 1.0f + s2 * (1.0f - sg) / two_sigma;                          // :53, the factor of v before `* dt`
+        w = s * sqrtf(-1.0f * dt);                                         // :62
+    }
+    __device__ float mean(float x, float v) const { return x * cx + v * cv * dt; }   // :53
+    __device__ float noise() const { return w; }                           // :62
+    __device__ float std() const { return s; }                             // std_dev_t, without the sqrt(-dt)
+    // d mean / d v, and grad_log_prob * d log_prob / d mean = grad_log_prob * (prev - mean) / (n w^2)
+    __device__ float dmu_dv() const { return cv * dt; }
+    __device__ float lp_scale(float glp, int64_t n) const { return glp / ((float)n * (w * w)) * dmu_dv(); }
+};
+
+template <class Step>
 __global__ __launch_bounds__(SDE_THREADS) void sde_step_kernel(
     const void* __restrict__ v_u, const void* __restrict__ v_t, int v_dt, float guidance,
     const void* __restrict__ x, int x_dt, const float* __restrict__ sigma,
-    const float* __restrict__ sigma_prev, int sigma_stride, float sin_coeff, int mode,
+    const float* __restrict__ sigma_prev, int sigma_stride, float level, const float* __restrict__ sigma_max, int mode,
     const float* __restrict__ eps, uint64_t seed, uint64_t offset,
     const void* __restrict__ prev, int prev_dt, float* __restrict__ out_next,
     void* __restrict__ out_cast, int cast_dt, float* __restrict__ out_mean,
     float* __restrict__ partial, float* __restrict__ out_std, int64_t n) {
     __shared__ float red[SDE_THREADS / 64];
     const int b = blockIdx.y;
-    const SdeCoef c = sde_coef(sigma, sigma_prev, sigma_stride, b, sin_coeff);
+    const Step c(sigma, sigma_prev, sigma_stride, b, level, sigma_max);
     const bool has_cfg = v_t != nullptr, bf = v_dt == ADVGRPO_BF16;
     const int64_t base = (int64_t)b * n;
     const Philox ph(seed);
@@ -109,12 +156,10 @@ __global__ __launch_bounds__(SDE_THREADS) void sde_step_kernel(
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const float v = cfg_v(vu[k], vt[k], has_cfg, bf, guidance);
-            const float x0 = xs[k] - c.sigma * v;              // :119
-            const float x1 = xs[k] + v * c.one_m_sigma;         // :120
-            mean[k] = x0 * c.one_m_sigma_prev + x1 * c.sq;     // :121
-            nxt[k] = (mode == ADVGRPO_SDE_REPLAY) ? e[k] : mean[k] + c.std * e[k];  // :131
+            mean[k] = c.mean(xs[k], v);
+            nxt[k] = (mode == ADVGRPO_SDE_REPLAY) ? e[k] : mean[k] + c.noise() * e[k];
             const float d = nxt[k] - mean[k];
-            acc += d * d;                                       // :134 (negated at finalize)
+            acc += d * d;                                       // :134, :65 (sign and scale at finalize)
         }
         if (out_next && mode != ADVGRPO_SDE_REPLAY) store8(out_next, ADVGRPO_F32, base + i, nxt);
         if (out_cast && mode != ADVGRPO_SDE_REPLAY) store8(out_cast, cast_dt, base + i, nxt);
@@ -123,7 +168,7 @@ __global__ __launch_bounds__(SDE_THREADS) void sde_step_kernel(
     const float tot = block_sum<SDE_THREADS / 64>(acc, red);
     if (threadIdx.x == 0) {
         partial[b * gridDim.x + blockIdx.x] = tot;
-        if (blockIdx.x == 0 && out_std) out_std[b] = c.std;
+        if (blockIdx.x == 0 && out_std) out_std[b] = c.std();
     }
 }
 
@@ -133,10 +178,11 @@ __global__ __launch_bounds__(SDE_THREADS) void sde_step_kernel(
 // operations in the same order on them, so every output -- the block partials of log_prob included -- has the bits of sde_step_kernel on
 // the materialised repeat.  The 16 B of v_u, v_t and x per lane are loaded, and the mean is computed, once per chunk for up to
 // SDE_BRANCH_COPIES copies; the copies' running sums live in lane-private LDS slots (a runtime-indexed register array would go to scratch).
+template <class Step>
 __global__ __launch_bounds__(SDE_THREADS) void sde_step_branch_kernel(
     const void* __restrict__ v_u, const void* __restrict__ v_t, int v_dt, float guidance,
     const void* __restrict__ x, int x_dt, const float* __restrict__ sigma,
-    const float* __restrict__ sigma_prev, int sigma_stride, float sin_coeff, int mode,
+    const float* __restrict__ sigma_prev, int sigma_stride, float level, const float* __restrict__ sigma_max, int mode,
     const float* __restrict__ eps, uint64_t seed, uint64_t offset,
     const void* __restrict__ prev, int prev_dt, float* __restrict__ out_next,
     void* __restrict__ out_cast, int cast_dt, float* __restrict__ out_mean,
@@ -146,7 +192,7 @@ __global__ __launch_bounds__(SDE_THREADS) void sde_step_branch_kernel(
     const int p = blockIdx.y;
     const int g0 = blockIdx.z * SDE_BRANCH_COPIES;
     const int ng = G - g0 < SDE_BRANCH_COPIES ? G - g0 : SDE_BRANCH_COPIES;
-    const SdeCoef c = sde_coef(sigma, sigma_prev, sigma_stride, p, sin_coeff);
+    const Step c(sigma, sigma_prev, sigma_stride, p, level, sigma_max);
     const bool has_cfg = v_t != nullptr, bf = v_dt == ADVGRPO_BF16;
     const int64_t in_base = (int64_t)p * n;
     const Philox ph(seed);
@@ -160,9 +206,7 @@ __global__ __launch_bounds__(SDE_THREADS) void sde_step_branch_kernel(
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const float v = cfg_v(vu[k], vt[k], has_cfg, bf, guidance);
-            const float x0 = xs[k] - c.sigma * v;              // :119
-            const float x1 = xs[k] + v * c.one_m_sigma;         // :120
-            mean[k] = x0 * c.one_m_sigma_prev + x1 * c.sq;     // :121
+            mean[k] = c.mean(xs[k], v);
         }
         for (int gg = 0; gg < ng; ++gg) {
             const int64_t o = ((int64_t)(g0 + gg) * P + p) * n + i;   // element (j, i) of the P * G-row outputs
@@ -178,9 +222,9 @@ __global__ __launch_bounds__(SDE_THREADS) void sde_step_branch_kernel(
             float acc = accs[gg][threadIdx.x];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                nxt[k] = (mode == ADVGRPO_SDE_REPLAY) ? e[k] : mean[k] + c.std * e[k];  // :131
+                nxt[k] = (mode == ADVGRPO_SDE_REPLAY) ? e[k] : mean[k] + c.noise() * e[k];
                 const float d = nxt[k] - mean[k];
-                acc += d * d;                                       // :134 (negated at finalize)
+                acc += d * d;                                       // :134, :65 (sign and scale at finalize)
             }
             accs[gg][threadIdx.x] = acc;
             if (out_next && mode != ADVGRPO_SDE_REPLAY) store8(out_next, ADVGRPO_F32, o, nxt);
@@ -193,7 +237,7 @@ __global__ __launch_bounds__(SDE_THREADS) void sde_step_branch_kernel(
         if (threadIdx.x == 0) {
             const int64_t j = (int64_t)(g0 + gg) * P + p;
             partial[j * gridDim.x + blockIdx.x] = tot;
-            if (blockIdx.x == 0 && out_std) out_std[j] = c.std;
+            if (blockIdx.x == 0 && out_std) out_std[j] = c.std();
         }
     }
 }
@@ -208,21 +252,35 @@ __global__ void sde_finalize_kernel(const float* __restrict__ partial, int nblk,
     out_log_prob[b] = (float)((double)sign * (s / (double)n));
 }
 
+// Flow-SDE: log_prob[b] = -(sum of block partials) / (n * 2 w^2) - log w - log sqrt(2 pi)   (SDE:64-71); row b takes the schedule row b % P.
+// noise_level == 0: w == 0 and the sum is 0, so this is 0/0 - log 0 = NaN, as in the reference.
+__global__ void flow_sde_finalize_kernel(const float* __restrict__ partial, int nblk, int64_t n, float* __restrict__ out_log_prob, int B,
+                                         const float* __restrict__ sigma, const float* __restrict__ sigma_prev, int sigma_stride, int P,
+                                         float noise_level, const float* __restrict__ sigma_max) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const FlowStep c(sigma, sigma_prev, sigma_stride, b % P, noise_level, sigma_max);
+    double s = 0.0;
+    for (int i = 0; i < nblk; ++i) s += (double)partial[b * nblk + i];
+    const double two_w2 = (double)(2.0f * (c.w * c.w));                    // :65, the reference's f32 denominator
+    out_log_prob[b] = (float)(-(s / (double)n) / two_w2 - log((double)c.w) - 0.91893853320467274178);
+}
+
+template <class Step>
 __global__ __launch_bounds__(SDE_THREADS) void sde_step_bwd_kernel(
     const void* __restrict__ v_u, const void* __restrict__ v_t, int v_dt, float guidance,
     const void* __restrict__ x, int x_dt, const float* __restrict__ sigma,
-    const float* __restrict__ sigma_prev, int sigma_stride, float sin_coeff,
+    const float* __restrict__ sigma_prev, int sigma_stride, float level, const float* __restrict__ sigma_max,
     const void* __restrict__ prev, int prev_dt, const float* __restrict__ grad_lp,
     void* __restrict__ g_u, void* __restrict__ g_t, int64_t n,
     const float* __restrict__ mean_ref, float kl_weight, int B, float* __restrict__ kl_partial) {
     __shared__ float red[SDE_THREADS / 64];
     const int b = blockIdx.y;
-    const SdeCoef c = sde_coef(sigma, sigma_prev, sigma_stride, b, sin_coeff);
+    const Step c(sigma, sigma_prev, sigma_stride, b, level, sigma_max);
     const bool has_cfg = v_t != nullptr, bf = v_dt == ADVGRPO_BF16;
     const int64_t base = (int64_t)b * n;
-    // d mean / d v, and d log_prob / d mean = 2 (prev - mean) / n
-    const float dmu_dv = c.one_m_sigma * c.sq - c.sigma * c.one_m_sigma_prev;
-    const float scale = grad_lp[b] * 2.0f / (float)n * dmu_dv;
+    const float dmu_dv = c.dmu_dv();
+    const float scale = c.lp_scale(grad_lp[b], n);
     // KL term (TP:1105-1108,1126-1130): loss += beta * mean_b mean_elem (mean - mean_ref)^2, mean_ref = the same step's mean
     // under the adapter-free transformer; d/d mean = beta * 2 (mean - mean_ref) / (n B), then the same d mean / d v
     const float kl_scale = mean_ref ? kl_weight * 2.0f / ((float)n * (float)B) * dmu_dv : 0.f;
@@ -238,9 +296,7 @@ __global__ __launch_bounds__(SDE_THREADS) void sde_step_bwd_kernel(
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const float v = cfg_v(vu[k], vt[k], has_cfg, bf, guidance);
-            const float x0 = xs[k] - c.sigma * v;
-            const float x1 = xs[k] + v * c.one_m_sigma;
-            const float mean = x0 * c.one_m_sigma_prev + x1 * c.sq;
+            const float mean = c.mean(xs[k], v);
             float gv = scale * (pv[k] - mean);
             if (mean_ref) {
                 const float d = mean - mr[k];
@@ -299,27 +355,104 @@ static int check_common(int v_dtype, int x_dtype, int B, int64_t n) {
     return 0;
 }
 
+// The four entry shapes, once for both steps.  Step = CpsStep: level = sin_coeff, sigma_max unused (NULL); Step = FlowStep: level =
+// noise_level, sigma_max required.  `what` names the entry in error messages.
+template <class Step>
+static int step_finalize(const float* ws, int nb, int64_t n, float* out_log_prob, int B, const float* sigma, const float* sigma_prev,
+                         int sigma_stride, int P, float level, const float* sigma_max, void* stream) {
+    if constexpr (std::is_same_v<Step, FlowStep>) {
+        hipLaunchKernelGGL(flow_sde_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream), ws, nb, n, out_log_prob, B,
+                           sigma, sigma_prev, sigma_stride, P, level, sigma_max);
+    } else {
+        hipLaunchKernelGGL(sde_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream), ws, nb, n, out_log_prob, B, -1.0f);
+    }
+    ADVGRPO_LAUNCH_CHECK();
+    return 0;
+}
+
+template <class Step>
+static int step_fwd(const char* what, const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale, const void* x,
+                    int x_dtype, const float* sigma, const float* sigma_prev, int sigma_stride, float level,
+                    const float* sigma_max, int mode, const float* eps, uint64_t seed, uint64_t offset, const void* prev_sample,
+                    int prev_dtype, float* out_next_f32, void* out_next_cast, int out_cast_dtype, float* out_mean,
+                    float* out_log_prob, float* out_std, void* workspace, int B, int64_t n, void* stream) {
+    if (check_common(v_dtype, x_dtype, B, n)) return -1;
+    ADVGRPO_CHECK(v_uncond && x && sigma && sigma_prev && out_log_prob && workspace, "%s: null argument", what);
+    ADVGRPO_CHECK((!std::is_same_v<Step, FlowStep>) || sigma_max, "%s: null sigma_max", what);
+    ADVGRPO_CHECK(mode >= 0 && mode <= 2, "%s: bad mode %d", what, mode);
+    ADVGRPO_CHECK(mode != ADVGRPO_SDE_EPS || eps, "%s: mode EPS needs eps", what);
+    ADVGRPO_CHECK(mode != ADVGRPO_SDE_REPLAY || prev_sample, "%s: mode REPLAY needs prev_sample", what);
+    const int nb = sde_blocks(n);
+    hipLaunchKernelGGL(sde_step_kernel<Step>, dim3(nb, B), dim3(SDE_THREADS), 0, as_stream(stream), v_uncond, v_text,
+                       v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride, level, sigma_max, mode, eps,
+                       seed, offset, prev_sample, prev_dtype, out_next_f32, out_next_cast, out_cast_dtype, out_mean,
+                       (float*)workspace, out_std, n);
+    ADVGRPO_LAUNCH_CHECK();
+    return step_finalize<Step>((const float*)workspace, nb, n, out_log_prob, B, sigma, sigma_prev, sigma_stride, B, level, sigma_max,
+                               stream);
+}
+
+template <class Step>
+static int step_branch(const char* what, const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale, const void* x,
+                       int x_dtype, const float* sigma, const float* sigma_prev, int sigma_stride, float level,
+                       const float* sigma_max, int mode, const float* eps, uint64_t seed, uint64_t offset,
+                       const void* prev_sample, int prev_dtype, float* out_next_f32, void* out_next_cast, int out_cast_dtype,
+                       float* out_mean, float* out_log_prob, float* out_std, void* workspace, int P, int G, int64_t n,
+                       void* stream) {
+    ADVGRPO_CHECK(P > 0 && G > 0, "%s: need P>0 and G>0 (P=%d G=%d)", what, P, G);
+    if (check_common(v_dtype, x_dtype, P, n)) return -1;
+    const int gz = (G + SDE_BRANCH_COPIES - 1) / SDE_BRANCH_COPIES;
+    ADVGRPO_CHECK(P <= 65535 && gz <= 65535 && (int64_t)P * G <= INT32_MAX, "%s: P=%d G=%d too large", what, P, G);
+    ADVGRPO_CHECK(v_uncond && x && sigma && sigma_prev && out_log_prob && workspace, "%s: null argument", what);
+    ADVGRPO_CHECK((!std::is_same_v<Step, FlowStep>) || sigma_max, "%s: null sigma_max", what);
+    ADVGRPO_CHECK(mode >= 0 && mode <= 2, "%s: bad mode %d", what, mode);
+    ADVGRPO_CHECK(mode != ADVGRPO_SDE_EPS || eps, "%s: mode EPS needs eps", what);
+    ADVGRPO_CHECK(mode != ADVGRPO_SDE_REPLAY || prev_sample, "%s: mode REPLAY needs prev_sample", what);
+    const int nb = sde_blocks(n), B = P * G;
+    hipLaunchKernelGGL(sde_step_branch_kernel<Step>, dim3(nb, P, gz), dim3(SDE_THREADS), 0, as_stream(stream), v_uncond, v_text,
+                       v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride, level, sigma_max, mode, eps,
+                       seed, offset, prev_sample, prev_dtype, out_next_f32, out_next_cast, out_cast_dtype, out_mean,
+                       (float*)workspace, out_std, P, G, n);
+    ADVGRPO_LAUNCH_CHECK();
+    return step_finalize<Step>((const float*)workspace, nb, n, out_log_prob, B, sigma, sigma_prev, sigma_stride, P, level, sigma_max,
+                               stream);
+}
+
+// mean_ref == NULL: the policy-only backward (kl_weight, kl_out and workspace unused)
+template <class Step>
+static int step_bwd(const char* what, const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale, const void* x,
+                    int x_dtype, const float* sigma, const float* sigma_prev, int sigma_stride, float level,
+                    const float* sigma_max, const void* prev_sample, int prev_dtype, const float* grad_log_prob, bool with_kl,
+                    const float* mean_ref, float kl_weight, void* grad_v_uncond, void* grad_v_text, float* kl_out, void* workspace,
+                    int B, int64_t n, void* stream) {
+    if (check_common(v_dtype, x_dtype, B, n)) return -1;
+    ADVGRPO_CHECK(v_uncond && x && sigma && sigma_prev && prev_sample && grad_log_prob && grad_v_uncond &&
+                      (!with_kl || (mean_ref && kl_out && workspace)), "%s: null argument", what);
+    ADVGRPO_CHECK((!std::is_same_v<Step, FlowStep>) || sigma_max, "%s: null sigma_max", what);
+    ADVGRPO_CHECK(!v_text || grad_v_text, "%s: CFG needs grad_v_text", what);
+    const int nb = sde_blocks(n);
+    hipLaunchKernelGGL(sde_step_bwd_kernel<Step>, dim3(nb, B), dim3(SDE_THREADS), 0, as_stream(stream), v_uncond, v_text,
+                       v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride, level, sigma_max, prev_sample,
+                       prev_dtype, grad_log_prob, grad_v_uncond, grad_v_text, n, with_kl ? mean_ref : (const float*)nullptr,
+                       with_kl ? kl_weight : 0.f, B, with_kl ? (float*)workspace : (float*)nullptr);
+    ADVGRPO_LAUNCH_CHECK();
+    if (with_kl) {
+        hipLaunchKernelGGL(sde_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream),
+                           (const float*)workspace, nb, n, kl_out, B, 1.0f);
+        ADVGRPO_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
 extern "C" int advgrpo_sde_step(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
                                 const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
                                 int sigma_stride, float sin_coeff, int mode, const float* eps, uint64_t seed,
                                 uint64_t offset, const void* prev_sample, int prev_dtype, float* out_next_f32,
                                 void* out_next_cast, int out_cast_dtype, float* out_mean, float* out_log_prob,
                                 float* out_std, void* workspace, int B, int64_t n, void* stream) {
-    if (check_common(v_dtype, x_dtype, B, n)) return -1;
-    ADVGRPO_CHECK(v_uncond && x && sigma && sigma_prev && out_log_prob && workspace, "sde_step: null argument");
-    ADVGRPO_CHECK(mode >= 0 && mode <= 2, "sde_step: bad mode %d", mode);
-    ADVGRPO_CHECK(mode != ADVGRPO_SDE_EPS || eps, "sde_step: mode EPS needs eps");
-    ADVGRPO_CHECK(mode != ADVGRPO_SDE_REPLAY || prev_sample, "sde_step: mode REPLAY needs prev_sample");
-    const int nb = sde_blocks(n);
-    hipLaunchKernelGGL(sde_step_kernel, dim3(nb, B), dim3(SDE_THREADS), 0, as_stream(stream), v_uncond, v_text,
-                       v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride, sin_coeff, mode, eps,
-                       seed, offset, prev_sample, prev_dtype, out_next_f32, out_next_cast, out_cast_dtype, out_mean,
-                       (float*)workspace, out_std, n);
-    ADVGRPO_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sde_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream),
-                       (const float*)workspace, nb, n, out_log_prob, B);
-    ADVGRPO_LAUNCH_CHECK();
-    return 0;
+    return step_fwd<CpsStep>("sde_step", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride,
+                             sin_coeff, nullptr, mode, eps, seed, offset, prev_sample, prev_dtype, out_next_f32, out_next_cast,
+                             out_cast_dtype, out_mean, out_log_prob, out_std, workspace, B, n, stream);
 }
 
 extern "C" int advgrpo_sde_step_branch(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
@@ -328,24 +461,9 @@ extern "C" int advgrpo_sde_step_branch(const void* v_uncond, const void* v_text,
                                        uint64_t offset, const void* prev_sample, int prev_dtype, float* out_next_f32,
                                        void* out_next_cast, int out_cast_dtype, float* out_mean, float* out_log_prob,
                                        float* out_std, void* workspace, int P, int G, int64_t n, void* stream) {
-    ADVGRPO_CHECK(P > 0 && G > 0, "sde_step_branch: need P>0 and G>0 (P=%d G=%d)", P, G);
-    if (check_common(v_dtype, x_dtype, P, n)) return -1;
-    const int gz = (G + SDE_BRANCH_COPIES - 1) / SDE_BRANCH_COPIES;
-    ADVGRPO_CHECK(P <= 65535 && gz <= 65535 && (int64_t)P * G <= INT32_MAX, "sde_step_branch: P=%d G=%d too large", P, G);
-    ADVGRPO_CHECK(v_uncond && x && sigma && sigma_prev && out_log_prob && workspace, "sde_step_branch: null argument");
-    ADVGRPO_CHECK(mode >= 0 && mode <= 2, "sde_step_branch: bad mode %d", mode);
-    ADVGRPO_CHECK(mode != ADVGRPO_SDE_EPS || eps, "sde_step_branch: mode EPS needs eps");
-    ADVGRPO_CHECK(mode != ADVGRPO_SDE_REPLAY || prev_sample, "sde_step_branch: mode REPLAY needs prev_sample");
-    const int nb = sde_blocks(n), B = P * G;
-    hipLaunchKernelGGL(sde_step_branch_kernel, dim3(nb, P, gz), dim3(SDE_THREADS), 0, as_stream(stream), v_uncond, v_text,
-                       v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride, sin_coeff, mode, eps,
-                       seed, offset, prev_sample, prev_dtype, out_next_f32, out_next_cast, out_cast_dtype, out_mean,
-                       (float*)workspace, out_std, P, G, n);
-    ADVGRPO_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sde_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream),
-                       (const float*)workspace, nb, n, out_log_prob, B);
-    ADVGRPO_LAUNCH_CHECK();
-    return 0;
+    return step_branch<CpsStep>("sde_step_branch", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev,
+                                sigma_stride, sin_coeff, nullptr, mode, eps, seed, offset, prev_sample, prev_dtype, out_next_f32,
+                                out_next_cast, out_cast_dtype, out_mean, out_log_prob, out_std, workspace, P, G, n, stream);
 }
 
 extern "C" int advgrpo_sde_step_bwd(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
@@ -353,16 +471,9 @@ extern "C" int advgrpo_sde_step_bwd(const void* v_uncond, const void* v_text, in
                                     int sigma_stride, float sin_coeff, const void* prev_sample, int prev_dtype,
                                     const float* grad_log_prob, void* grad_v_uncond, void* grad_v_text, int B,
                                     int64_t n, void* stream) {
-    if (check_common(v_dtype, x_dtype, B, n)) return -1;
-    ADVGRPO_CHECK(v_uncond && x && sigma && sigma_prev && prev_sample && grad_log_prob && grad_v_uncond,
-                  "sde_step_bwd: null argument");
-    ADVGRPO_CHECK(!v_text || grad_v_text, "sde_step_bwd: CFG needs grad_v_text");
-    hipLaunchKernelGGL(sde_step_bwd_kernel, dim3(sde_blocks(n), B), dim3(SDE_THREADS), 0, as_stream(stream),
-                       v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride,
-                       sin_coeff, prev_sample, prev_dtype, grad_log_prob, grad_v_uncond, grad_v_text, n,
-                       (const float*)nullptr, 0.f, B, (float*)nullptr);
-    ADVGRPO_LAUNCH_CHECK();
-    return 0;
+    return step_bwd<CpsStep>("sde_step_bwd", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride,
+                             sin_coeff, nullptr, prev_sample, prev_dtype, grad_log_prob, false, nullptr, 0.f, grad_v_uncond,
+                             grad_v_text, nullptr, nullptr, B, n, stream);
 }
 
 extern "C" int advgrpo_sde_step_bwd_kl(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
@@ -371,20 +482,54 @@ extern "C" int advgrpo_sde_step_bwd_kl(const void* v_uncond, const void* v_text,
                                        const float* grad_log_prob, const float* mean_ref, float kl_weight,
                                        void* grad_v_uncond, void* grad_v_text, float* kl_out, void* workspace, int B,
                                        int64_t n, void* stream) {
-    if (check_common(v_dtype, x_dtype, B, n)) return -1;
-    ADVGRPO_CHECK(v_uncond && x && sigma && sigma_prev && prev_sample && grad_log_prob && grad_v_uncond && mean_ref &&
-                      kl_out && workspace, "sde_step_bwd_kl: null argument");
-    ADVGRPO_CHECK(!v_text || grad_v_text, "sde_step_bwd_kl: CFG needs grad_v_text");
-    const int nb = sde_blocks(n);
-    hipLaunchKernelGGL(sde_step_bwd_kernel, dim3(nb, B), dim3(SDE_THREADS), 0, as_stream(stream), v_uncond, v_text,
-                       v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride, sin_coeff, prev_sample,
-                       prev_dtype, grad_log_prob, grad_v_uncond, grad_v_text, n, mean_ref, kl_weight, B,
-                       (float*)workspace);
-    ADVGRPO_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sde_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream),
-                       (const float*)workspace, nb, n, kl_out, B, 1.0f);
-    ADVGRPO_LAUNCH_CHECK();
-    return 0;
+    return step_bwd<CpsStep>("sde_step_bwd_kl", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev,
+                             sigma_stride, sin_coeff, nullptr, prev_sample, prev_dtype, grad_log_prob, true, mean_ref, kl_weight,
+                             grad_v_uncond, grad_v_text, kl_out, workspace, B, n, stream);
+}
+
+extern "C" int advgrpo_flow_sde_step(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                     const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                     int sigma_stride, float noise_level, const float* sigma_max, int mode, const float* eps,
+                                     uint64_t seed, uint64_t offset, const void* prev_sample, int prev_dtype,
+                                     float* out_next_f32, void* out_next_cast, int out_cast_dtype, float* out_mean,
+                                     float* out_log_prob, float* out_std, void* workspace, int B, int64_t n, void* stream) {
+    return step_fwd<FlowStep>("flow_sde_step", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride,
+                              noise_level, sigma_max, mode, eps, seed, offset, prev_sample, prev_dtype, out_next_f32, out_next_cast,
+                              out_cast_dtype, out_mean, out_log_prob, out_std, workspace, B, n, stream);
+}
+
+extern "C" int advgrpo_flow_sde_step_branch(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                            const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                            int sigma_stride, float noise_level, const float* sigma_max, int mode,
+                                            const float* eps, uint64_t seed, uint64_t offset, const void* prev_sample,
+                                            int prev_dtype, float* out_next_f32, void* out_next_cast, int out_cast_dtype,
+                                            float* out_mean, float* out_log_prob, float* out_std, void* workspace, int P, int G,
+                                            int64_t n, void* stream) {
+    return step_branch<FlowStep>("flow_sde_step_branch", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev,
+                                 sigma_stride, noise_level, sigma_max, mode, eps, seed, offset, prev_sample, prev_dtype,
+                                 out_next_f32, out_next_cast, out_cast_dtype, out_mean, out_log_prob, out_std, workspace, P, G, n,
+                                 stream);
+}
+
+extern "C" int advgrpo_flow_sde_step_bwd(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                         const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                         int sigma_stride, float noise_level, const float* sigma_max, const void* prev_sample,
+                                         int prev_dtype, const float* grad_log_prob, void* grad_v_uncond, void* grad_v_text,
+                                         int B, int64_t n, void* stream) {
+    return step_bwd<FlowStep>("flow_sde_step_bwd", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev,
+                              sigma_stride, noise_level, sigma_max, prev_sample, prev_dtype, grad_log_prob, false, nullptr, 0.f,
+                              grad_v_uncond, grad_v_text, nullptr, nullptr, B, n, stream);
+}
+
+extern "C" int advgrpo_flow_sde_step_bwd_kl(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                            const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                            int sigma_stride, float noise_level, const float* sigma_max,
+                                            const void* prev_sample, int prev_dtype, const float* grad_log_prob,
+                                            const float* mean_ref, float kl_weight, void* grad_v_uncond, void* grad_v_text,
+                                            float* kl_out, void* workspace, int B, int64_t n, void* stream) {
+    return step_bwd<FlowStep>("flow_sde_step_bwd_kl", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev,
+                              sigma_stride, noise_level, sigma_max, prev_sample, prev_dtype, grad_log_prob, true, mean_ref,
+                              kl_weight, grad_v_uncond, grad_v_text, kl_out, workspace, B, n, stream);
 }
 
 extern "C" int advgrpo_randn(void* out, int out_dtype, int64_t n, uint64_t seed, uint64_t offset, void* stream) {

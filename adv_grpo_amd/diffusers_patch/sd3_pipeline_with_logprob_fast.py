@@ -33,11 +33,13 @@ def pipeline_with_logprob_random(self, prompt=None, prompt_2=None, prompt_3=None
                                  joint_attention_kwargs=None, clip_skip=None,
                                  callback_on_step_end_tensor_inputs=("latents",), max_sequence_length=256,
                                  skip_layer_guidance_scale=2.8, noise_level=0.7, train_num_steps=1, process_index=0,
-                                 sample_num_steps=10, random_timestep=None, noises=None, seed=None):
+                                 sample_num_steps=10, random_timestep=None, noises=None, seed=None, sde_type="cps"):
+    """``sde_type``: ``"cps"`` (Flow-CPS, the reference's step for this rollout) or ``"sde"`` (Flow-SDE, SDE:13-73) for the steps of the window;
+    the default reproduces the bits this function always gave."""
     return rollout(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, height, width,
                    num_inference_steps, mini_num_image_per_prompt, guidance_scale, generator, latents, output_type, joint_attention_kwargs,
                    noise_level, train_num_steps, process_index, sample_num_steps, random_timestep, noises, seed,
-                   branch=False, keep_f32=False)
+                   branch=False, keep_f32=False, sde_type=sde_type)
 
 
 @torch.no_grad()
@@ -67,11 +69,13 @@ def pipeline_with_logprob_new(self, prompt=None, prompt_2=None, prompt_3=None, h
       pipeline_with_logprob_random for P * G rows, so ``mini_num_image_per_prompt=1`` returns that function's bits for the same ``seed``.
     * ``output_type``: ``"pil"`` (the reference's default) a list of PIL images, ``"latent"`` the final latents undecoded (as
       pipeline_with_logprob_random), anything else the [0, 1] image tensor.
+    * the keyword list is the reference's plus ``noises`` / ``seed`` and nothing else, so the choice of step travels on the pipeline object,
+      like ``cfg_two_streams``: ``self.sde_type`` = ``"cps"`` (the default when absent) or ``"sde"`` (Flow-SDE, SDE:13-73).
     The G samples of a group share their initial noise and prefix: the group's spread comes from the SDE window alone."""
     return rollout(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, height, width,
                    num_inference_steps, mini_num_image_per_prompt, guidance_scale, generator, latents, output_type, joint_attention_kwargs,
                    noise_level, train_num_steps, process_index, sample_num_steps, random_timestep, noises, seed,
-                   branch=True, keep_f32=False)
+                   branch=True, keep_f32=False, sde_type=getattr(self, "sde_type", "cps"))
 
 
 @torch.no_grad()
@@ -92,4 +96,4 @@ def pipeline_with_logprob(self, prompt=None, prompt_2=None, prompt_3=None, heigh
     return rollout(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, height, width,
                    num_inference_steps, mini_num_image_per_prompt, guidance_scale, generator, latents, output_type, joint_attention_kwargs,
                    noise_level, train_num_steps, process_index, sample_num_steps, random_timestep, noises, seed,
-                   branch=True, keep_f32=True)
+                   branch=True, keep_f32=True, sde_type=getattr(self, "sde_type", "cps"))

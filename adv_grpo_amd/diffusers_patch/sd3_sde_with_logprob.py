@@ -1,15 +1,22 @@
-"""Flow-CPS SDE step with per-sample log-prob on the fused gfx950 kernel.
+"""Flow-CPS and Flow-SDE steps with per-sample log-prob on the fused gfx950 kernel.
 
 Drop-in for adv_grpo/diffusers_patch/sd3_sde_with_logprob.py:77-139 (same name, argument
 meaning and return tuple).  ``sde_step_cfg`` is the fused entry the rollout uses: it also
 folds the CFG combine and the cast back to the latent dtype
 (sd3_pipeline_with_logprob_fast.py:640-655) into the same HBM pass.
+
+Names: ``sde_step_with_logprob`` and ``sde_step_with_logprob_new`` both mean Flow-CPS here (what the reference's rollouts import under
+either name).  The reference's own ``sde_step_with_logprob`` (SDE:13-73, the original Flow-GRPO step with the full Gaussian log-density) is
+``flow_sde_step_with_logprob``; ``sde_step_cfg(sde_type="sde")`` is its fused form.
 """
 import math
 
 import torch
 
 from .. import _lib
+
+
+SDE_TYPES = ("cps", "sde")
 
 
 def _sigma_tables(scheduler, timestep, B, device):
@@ -26,7 +33,7 @@ def _sigma_tables(scheduler, timestep, B, device):
 
 def sde_step_cfg(scheduler, v_uncond, v_text, guidance_scale, timestep, sample, noise_level=0.7,
                  prev_sample=None, noise=None, seed=None, offset=0, out_dtype=None, want_mean=True,
-                 step_index=None, sigmas=None, copies=None):
+                 step_index=None, sigmas=None, copies=None, sde_type="cps"):
     """Returns (prev_sample_f32_or_None, prev_sample_cast_or_None, log_prob, prev_sample_mean_or_None, std_dev_t).
 
     v_text=None => no CFG.  Exactly one of prev_sample (replay), noise (injected epsilon) or seed
@@ -34,15 +41,22 @@ def sde_step_cfg(scheduler, v_uncond, v_text, guidance_scale, timestep, sample, 
 
     copies=G: the fan-out step of the branching rollouts (advgrpo_sde_step_branch).  v_uncond / v_text / sample hold P rows,
     noise / prev_sample and every output P * G rows; output row j continues input row j % P (``sample.repeat(G, 1, 1, 1)``)
-    with its own epsilon -- the bits of this function on the repeated inputs, without the repeat and with one read of them."""
+    with its own epsilon -- the bits of this function on the repeated inputs, without the repeat and with one read of them.
+
+    sde_type: "cps" (Flow-CPS, SDE:117-134: log_prob = -mean((x' - mean)^2)) or "sde" (Flow-SDE, SDE:44-71: the Gaussian log-density with
+    its 1 / (2 w^2), log w and log sqrt(2 pi) terms; std_dev_t is returned without the sqrt(-dt)).  With "sde" and noise_level == 0 the
+    step is the deterministic x + v * dt and log_prob is NaN, as in the reference."""
+    if sde_type not in SDE_TYPES:
+        raise ValueError(f"sde_step_cfg: sde_type must be one of {SDE_TYPES}, got {sde_type!r}")
+    flow = sde_type == "sde"
     lib = _lib.load()
     P = sample.shape[0]
     B = P if copies is None else P * int(copies)
     out_shape = (B, *sample.shape[1:])
     n = sample[0].numel()
     dev = sample.device
+    tab = scheduler.sigmas if sigmas is None else sigmas           # `sigmas`: the caller's rollout-local table
     if step_index is not None:
-        tab = scheduler.sigmas if sigmas is None else sigmas       # `sigmas`: the caller's rollout-local table
         sig, sigp, stride = tab[step_index:step_index + 1], tab[step_index + 1:step_index + 2], 0
     else:
         sig, sigp, stride = _sigma_tables(scheduler, timestep, P, dev)
@@ -69,11 +83,16 @@ def sde_step_cfg(scheduler, v_uncond, v_text, guidance_scale, timestep, sample, 
     lp = torch.empty(B, dtype=torch.float32, device=dev)
     std = torch.empty(B, dtype=torch.float32, device=dev)
     ws = torch.empty(max(1, lib.advgrpo_sde_step_workspace_bytes(B, n) // 4), dtype=torch.float32, device=dev)
-    entry = lib.advgrpo_sde_step if copies is None else lib.advgrpo_sde_step_branch
+    if flow:                                                       # noise_level and a device pointer to sigma_max = sigmas[1] (SDE:46)
+        entry = lib.advgrpo_flow_sde_step if copies is None else lib.advgrpo_flow_sde_step_branch
+        level = (float(noise_level), _lib.ptr(tab[1:2]))
+    else:
+        entry = lib.advgrpo_sde_step if copies is None else lib.advgrpo_sde_step_branch
+        level = (float(math.sin(noise_level * math.pi / 2)),)
     _lib.check(entry(
         _lib.ptr(v_uncond), _lib.ptr(v_text), _lib.dtype_code(v_uncond.dtype), float(guidance_scale),
         _lib.ptr(sample), _lib.dtype_code(sample.dtype), _lib.ptr(sig), _lib.ptr(sigp), stride,
-        float(math.sin(noise_level * math.pi / 2)), mode, _lib.ptr(noise) if mode == _lib.SDE_EPS else None,
+        *level, mode, _lib.ptr(noise) if mode == _lib.SDE_EPS else None,
         int(seed or 0), int(offset), _lib.ptr(prev_sample) if replay else None,
         _lib.dtype_code(prev_sample.dtype) if replay else 0, _lib.ptr(nxt), _lib.ptr(cast),
         _lib.dtype_code(cast.dtype) if cast is not None else 0, _lib.ptr(mean), _lib.ptr(lp), _lib.ptr(std),
@@ -81,11 +100,7 @@ def sde_step_cfg(scheduler, v_uncond, v_text, guidance_scale, timestep, sample, 
     return nxt, cast, lp, mean, std.view(-1, *([1] * (sample.dim() - 1)))
 
 
-def sde_step_with_logprob(scheduler, model_output, timestep, sample, noise_level=0.7, prev_sample=None,
-                          generator=None, noise=None):
-    """Reference signature (sd3_sde_with_logprob.py:77-85); returns
-    (prev_sample, log_prob, prev_sample_mean, std_dev_t), all float32.
-    ``generator``: a torch.Generator whose next int64 seeds the in-kernel Philox stream."""
+def _step_with_logprob(sde_type, scheduler, model_output, timestep, sample, noise_level, prev_sample, generator, noise):
     seed = None
     if prev_sample is None and noise is None:
         if generator is not None:
@@ -93,10 +108,25 @@ def sde_step_with_logprob(scheduler, model_output, timestep, sample, noise_level
         else:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     nxt, _, lp, mean, std = sde_step_cfg(scheduler, model_output, None, 1.0, timestep, sample, noise_level,
-                                         prev_sample=prev_sample, noise=noise, seed=seed)
+                                         prev_sample=prev_sample, noise=noise, seed=seed, sde_type=sde_type)
     if prev_sample is not None:
         nxt = prev_sample.float()
     return nxt, lp, mean, std
 
 
+def sde_step_with_logprob(scheduler, model_output, timestep, sample, noise_level=0.7, prev_sample=None,
+                          generator=None, noise=None):
+    """Flow-CPS.  Reference signature (sd3_sde_with_logprob.py:77-85); returns
+    (prev_sample, log_prob, prev_sample_mean, std_dev_t), all float32.
+    ``generator``: a torch.Generator whose next int64 seeds the in-kernel Philox stream."""
+    return _step_with_logprob("cps", scheduler, model_output, timestep, sample, noise_level, prev_sample, generator, noise)
+
+
 sde_step_with_logprob_new = sde_step_with_logprob
+
+
+def flow_sde_step_with_logprob(scheduler, model_output, timestep, sample, noise_level=0.7, prev_sample=None,
+                               generator=None, noise=None):
+    """Flow-SDE: the reference's ``sde_step_with_logprob`` (sd3_sde_with_logprob.py:13-73), its signature (plus ``noise=``) and its return
+    tuple (prev_sample, log_prob, prev_sample_mean, std_dev_t), all float32; log_prob is the Gaussian log-density, mean over the elements."""
+    return _step_with_logprob("sde", scheduler, model_output, timestep, sample, noise_level, prev_sample, generator, noise)

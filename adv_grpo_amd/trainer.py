@@ -342,6 +342,13 @@ class Trainer:
         # opt-in `sample.branch_rollout`: the reference's shared-prefix rollout (PF:234-448) -- one latent through the noise-free prefix, repeated G
         # times at the first SDE step.  The G samples of a group then share their initial noise; the sample dict keeps its keys and shapes.
         rollout_fn = pipeline_with_logprob_new if c.sample.get("branch_rollout", False) else pipeline_with_logprob_random
+        # opt-in `sample.sde_type` ("cps" when absent, or "sde": the Flow-SDE step, SDE:13-73): a keyword of pipeline_with_logprob_random; the
+        # branching rollout, whose keyword list is the reference's, reads it from the pipeline object
+        sde_kw = {}
+        if rollout_fn is pipeline_with_logprob_new:
+            self.pipe.sde_type = c.sample.get("sde_type") or "cps"     # always assigned: the pipe never keeps an earlier Trainer's choice
+        elif c.sample.get("sde_type") is not None:
+            sde_kw = {"sde_type": c.sample.sde_type}
 
         def rollout(i, idx, pe, ppe, ref, prompts):
             images, lats, lps, tss = rollout_fn(
@@ -350,7 +357,7 @@ class Trainer:
                 guidance_scale=c.sample.guidance_scale, output_type="pt", height=c.resolution, width=c.resolution,
                 noise_level=c.sample.noise_level, mini_num_image_per_prompt=G, train_num_steps=T,
                 process_index=self.rank, sample_num_steps=c.sample.num_steps, random_timestep=c.sample.random_timestep,
-                seed=rollout_seed(c.seed, self.epoch * nb + i, self.rank))                  # TP:755-772
+                seed=rollout_seed(c.seed, self.epoch * nb + i, self.rank), **sde_kw)        # TP:755-772
             first = int(self.pipe.last_random_timestep)
             score_prompts = prompts
             if hasattr(self.data, "prompt_text"):          # host scorers (ocr) read the strings, PickScore the ids
@@ -469,7 +476,7 @@ class Trainer:
                     num_inference_steps=c.sample.eval_num_steps, guidance_scale=c.sample.guidance_scale, output_type="pt",
                     height=c.resolution, width=c.resolution, noise_level=0, mini_num_image_per_prompt=1,
                     process_index=self.rank, sample_num_steps=c.sample.num_steps, random_timestep=c.sample.random_timestep,
-                    generator=gen)                                                          # TP:303-320
+                    generator=gen, **({} if c.sample.get("sde_type") is None else {"sde_type": c.sample.sde_type}))   # TP:303-320
                 if save_folder is not None:
                     names = write_eval_images(images, save_folder, self.rank, batch_idx)    # eval.py:258-266
                     for i, name in zip(idxs, names):
@@ -650,7 +657,7 @@ class Trainer:
                         model, self.pipe.scheduler, s, j, embeds, pooled, s["log_probs"][:, j], s["advantages"][:, j],
                         guidance_scale=c.sample.guidance_scale, noise_level=c.sample.noise_level, adv_clip_max=c.train.adv_clip_max,
                         clip_range=c.train.clip_range, loss_scale=1.0 / (GA * T), step_index=samples["first_step_index"][i] + j,
-                        beta=c.train.beta))
+                        beta=c.train.beta, sde_type=c.sample.get("sde_type") or "cps"))
                     for k in ("loss", "approx_kl", "clipfrac", "clipfrac_gt_one", "clipfrac_lt_one", "policy_loss") + \
                             (("kl_loss",) if c.train.beta > 0 else ()):                     # TP:1158-1160
                         agg[k] = agg.get(k, 0) + info[k]

@@ -108,6 +108,64 @@ int advgrpo_sde_step_bwd_kl(const void* v_uncond, const void* v_text, int v_dtyp
                             void* grad_v_uncond, void* grad_v_text, float* kl_out, void* workspace, int B,
                             int64_t n, void* stream);
 
+/* ------------------------------------------------------------------ Flow-SDE step
+ * The original Flow-GRPO step, sd3_sde_with_logprob.py:13-73 (the reference's `sde_step_with_logprob`), as the sibling of the
+ * Flow-CPS entries above: the same kernels over another per-row arithmetic, the same modes, counters, CFG roundings, optional
+ * outputs and workspace (advgrpo_sde_step_workspace_bytes).  `noise_level` takes the place of sin_coeff; `sigma_max` is a
+ * device pointer to the schedule's sigmas[1] (:46, read on the device: no host sync).  Per row, every scalar one f32 rounding
+ * in the reference's operation order (`**2` is x*x, division and square root correctly rounded):
+ *
+ *   dt     = sigma_prev - sigma                                                                     (:47)
+ *   s      = sqrt(sigma / (1 - (sigma == 1 ? sigma_max : sigma))) * noise_level                     (:49)  -> out_std
+ *   mean   = x*(1 + s*s/(2*sigma)*dt) + v*(1 + s*s*(1-sigma)/(2*sigma))*dt                          (:53)  v after CFG
+ *   w      = s * sqrt(-dt)
+ *   next   = mode==REPLAY ? prev_sample : mean + w*eps                                              (:62)
+ *   log_prob[b] = mean_over_n( -(next-mean)^2 / (2*w*w) ) - log(w) - log(sqrt(2*pi))                (:64-71)
+ *
+ * mean / next are bit-exact with the reference's torch-CPU result; log_prob is (sum of squares)/n scaled once, so it differs
+ * by summation order and one rounding.  noise_level == 0: s = w = 0, next == mean = x + v*dt in the reference's bits and
+ * log_prob is NaN (0/0 - log 0), as the reference's is; nothing may consume it. */
+int advgrpo_flow_sde_step(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                          const void* x, int x_dtype,
+                          const float* sigma, const float* sigma_prev, int sigma_stride, float noise_level,
+                          const float* sigma_max,
+                          int mode, const float* eps, uint64_t seed, uint64_t offset,
+                          const void* prev_sample, int prev_dtype,
+                          float* out_next_f32, void* out_next_cast, int out_cast_dtype,
+                          float* out_mean, float* out_log_prob, float* out_std,
+                          void* workspace, int B, int64_t n, void* stream);
+
+/* Fan-out form, the contract of advgrpo_sde_step_branch: every output has the bits of advgrpo_flow_sde_step(B = P*G) on the
+ * materialised repeat, log_prob included, for any G. */
+int advgrpo_flow_sde_step_branch(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                 const void* x, int x_dtype,
+                                 const float* sigma, const float* sigma_prev, int sigma_stride, float noise_level,
+                                 const float* sigma_max,
+                                 int mode, const float* eps, uint64_t seed, uint64_t offset,
+                                 const void* prev_sample, int prev_dtype,
+                                 float* out_next_f32, void* out_next_cast, int out_cast_dtype,
+                                 float* out_mean, float* out_log_prob, float* out_std,
+                                 void* workspace, int P, int G, int64_t n, void* stream);
+
+/* Backward of the replay-mode Flow-SDE step.  With c_v = (1 + s*s*(1-sigma)/(2*sigma))*dt = d mean / d v:
+ *   g_v = grad_log_prob[b] * (prev-mean) * c_v / (n*w*w)
+ *   grad_v_text = guidance*g_v ; grad_v_uncond = (1-guidance)*g_v      (written in v_dtype, as advgrpo_sde_step_bwd) */
+int advgrpo_flow_sde_step_bwd(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                              const void* x, int x_dtype,
+                              const float* sigma, const float* sigma_prev, int sigma_stride, float noise_level,
+                              const float* sigma_max,
+                              const void* prev_sample, int prev_dtype, const float* grad_log_prob,
+                              void* grad_v_uncond, void* grad_v_text, int B, int64_t n, void* stream);
+/* The same backward with the KL term, as advgrpo_sde_step_bwd_kl: g_v += kl_weight * 2*(mean - mean_ref) * c_v / (n*B) before the
+ * bf16 rounding, kl_out[b] = mean_elem (mean - mean_ref)^2.  kl_weight == 0 gives the bits of advgrpo_flow_sde_step_bwd. */
+int advgrpo_flow_sde_step_bwd_kl(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                 const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                 int sigma_stride, float noise_level, const float* sigma_max,
+                                 const void* prev_sample, int prev_dtype,
+                                 const float* grad_log_prob, const float* mean_ref, float kl_weight,
+                                 void* grad_v_uncond, void* grad_v_text, float* kl_out, void* workspace, int B,
+                                 int64_t n, void* stream);
+
 /* ------------------------------------------------------------------ group advantage
  * PerPromptStatTracker.update(type='grpo') on a fresh tracker -- adv_grpo/stat_tracking.py:18-47:
  * float64, per-group mean over rows, std = global (np.std over all rows, per column) or

@@ -61,6 +61,9 @@ def build_parser():
                     help="sample.branch_rollout: roll a prompt group out with the reference's pipeline_with_logprob_new -- one latent through the "
                          "noise-free prefix, repeated at the first SDE step.  The images of a group then share their initial noise and prefix: "
                          "their spread comes from the SDE window alone")
+    ap.add_argument("--sde-type", default=None, choices=["cps", "sde"],
+                    help="sample.sde_type: the stochastic step of rollout and replay -- cps (Flow-CPS, the default when the config has no "
+                         "such key) or sde (the original Flow-GRPO SDE with the full Gaussian log-density)")
     ap.add_argument("--lora-mode", default="merged", choices=["merged", "side"],
                     help="merged: LoRA folded into the bf16 weights (default); side: PEFT's side-path arithmetic (TP:490-511)")
     ap.add_argument("--no-train-d", action="store_true", help="keep the discriminator frozen: every epoch is a G-step epoch")
@@ -131,6 +134,8 @@ def main():
         cfg.sample.cfg_two_streams = True
     if args.branch_rollout:
         cfg.sample.branch_rollout = True
+    if args.sde_type:
+        cfg.sample.sde_type = args.sde_type
     if args.no_train_d:
         cfg.train_d = False
     if args.batches:
