@@ -411,26 +411,8 @@ extern "C" int advgrpo_gemm_variant(int M, int N, int K, int batch, int conv) {
     return gemm_variant(M, N, K, batch < 1 ? 1 : batch, conv, !conv);
 }
 
-extern "C" int advgrpo_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
-                                 int out_dtype, int M, int N, int K, const void* bias, int act, float alpha,
-                                 const void* gate, int64_t gate_stride, int gate_rows, const void* residual,
-                                 int64_t ldr, int seg_rows, int64_t seg_stride, int64_t seg_off, int a_seg_rows,
-                                 int64_t a_seg_stride, int64_t a_seg_off, int batch, int64_t strideA,
-                                 int64_t strideW, int64_t strideC, void* stream) {
-    GemmParams p{};
-    p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.C = C;
-    p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.out_dtype = out_dtype;
-    p.M = M; p.N = N; p.K = K;
-    p.bias = (const bf16_t*)bias; p.act = act; p.alpha = alpha;
-    p.gate = (const bf16_t*)gate; p.gate_stride = gate_stride; p.gate_rows = gate_rows; p.gate_batch_stride = 0;
-    p.residual = (const bf16_t*)residual; p.ldr = ldr; p.strideR = strideC;
-    p.seg_rows = seg_rows; p.seg_stride = seg_stride; p.seg_off = seg_off;
-    p.a_seg_rows = a_seg_rows; p.a_seg_stride = a_seg_stride; p.a_seg_off = a_seg_off;
-    p.batch = batch < 1 ? 1 : batch; p.strideA = strideA; p.strideW = strideW; p.strideC = strideC;
-    p.splitk = 1;
-    return gemm_bf16(p, as_stream(stream));
-}
-
+// The one translation from the public descriptor to the kernel's parameter block.  Every Linear entry goes through it: a field added to
+// the epilogue is read here or nowhere.
 static GemmParams from_desc(const advgrpo_gemm_desc& d) {
     GemmParams p{};
     p.A = (const bf16_t*)d.A; p.W = (const bf16_t*)d.W; p.C = d.C;
@@ -446,6 +428,36 @@ static GemmParams from_desc(const advgrpo_gemm_desc& d) {
     p.rms_w = (const bf16_t*)d.rms_weight; p.rms_nheads = d.rms_nheads; p.rms_hpw = d.rms_heads_per_weight;
     p.rms_eps = d.rms_eps; p.rms_rs_out = d.rms_rs_out;
     return p;
+}
+
+// the flat entries' leading arguments as a descriptor (everything else zero)
+static advgrpo_gemm_desc flat_desc(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int out_dtype, int M,
+                                   int N, int K, const void* bias, int act, float alpha, const void* gate, int64_t gate_stride,
+                                   int gate_rows, const void* residual, int64_t ldr) {
+    advgrpo_gemm_desc d{};
+    d.A = A; d.W = W; d.C = C;
+    d.lda = lda; d.ldw = ldw; d.ldc = ldc; d.out_dtype = out_dtype;
+    d.M = M; d.N = N; d.K = K;
+    d.bias = bias; d.act = act; d.alpha = alpha;
+    d.gate = gate; d.gate_stride = gate_stride; d.gate_rows = gate_rows;
+    d.residual = residual; d.ldr = ldr;
+    return d;
+}
+
+extern "C" int advgrpo_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
+                                 int out_dtype, int M, int N, int K, const void* bias, int act, float alpha,
+                                 const void* gate, int64_t gate_stride, int gate_rows, const void* residual,
+                                 int64_t ldr, int seg_rows, int64_t seg_stride, int64_t seg_off, int a_seg_rows,
+                                 int64_t a_seg_stride, int64_t a_seg_off, int batch, int64_t strideA,
+                                 int64_t strideW, int64_t strideC, void* stream) {
+    advgrpo_gemm_desc d = flat_desc(A, lda, W, ldw, C, ldc, out_dtype, M, N, K, bias, act, alpha, gate, gate_stride, gate_rows, residual, ldr);
+    d.seg_rows = seg_rows; d.seg_stride = seg_stride; d.seg_off = seg_off;
+    d.a_seg_rows = a_seg_rows; d.a_seg_stride = a_seg_stride; d.a_seg_off = a_seg_off;
+    GemmParams p = from_desc(d);
+    // this entry alone: the batch (grid.y) with its strides; the residual steps with C, the gate is shared by the batch
+    p.batch = batch < 1 ? 1 : batch; p.strideA = strideA; p.strideW = strideW; p.strideC = strideC;
+    p.strideR = strideC; p.gate_batch_stride = 0;
+    return gemm_bf16(p, as_stream(stream));
 }
 
 extern "C" int advgrpo_gemm_grouped(const advgrpo_gemm_desc* descs, int count, void* stream) {
@@ -473,43 +485,43 @@ extern "C" int advgrpo_gemm_bf16_train(const void* A, int64_t lda, const void* W
                                        const void* gate, int64_t gate_stride, int gate_rows, const void* residual,
                                        int64_t ldr, void* aux_out, const void* aux_in, int64_t ld_aux, int splitk,
                                        void* stream) {
-    GemmParams p{};
-    p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.C = C;
-    p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.out_dtype = out_dtype;
-    p.M = M; p.N = N; p.K = K;
-    p.bias = (const bf16_t*)bias; p.act = act; p.alpha = alpha;
-    p.gate = (const bf16_t*)gate; p.gate_stride = gate_stride; p.gate_rows = gate_rows;
-    p.residual = (const bf16_t*)residual; p.ldr = ldr;
-    p.batch = 1; p.splitk = splitk < 1 ? 1 : splitk;
-    p.aux_out = (bf16_t*)aux_out; p.aux_in = (const bf16_t*)aux_in; p.ld_aux = ld_aux;
+    advgrpo_gemm_desc d = flat_desc(A, lda, W, ldw, C, ldc, out_dtype, M, N, K, bias, act, alpha, gate, gate_stride, gate_rows, residual, ldr);
+    d.aux_out = aux_out; d.aux_in = aux_in; d.ld_aux = ld_aux;
+    GemmParams p = from_desc(d);
+    p.splitk = splitk < 1 ? 1 : splitk;   // this entry alone: the K range split over grid.y
     return gemm_bf16(p, as_stream(stream));
 }
 
 /* C (f32) += alpha * A W^T, every element added by the one lane that owns it (no atomics: a fixed summation order) */
 extern "C" int advgrpo_gemm_bf16_acc_f32(const void* A, int64_t lda, const void* W, int64_t ldw, float* C, int64_t ldc, int M,
                                          int N, int K, float alpha, void* stream) {
-    GemmParams p{};
-    p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.C = C;
-    p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.out_dtype = ADVGRPO_F32;
-    p.M = M; p.N = N; p.K = K; p.alpha = alpha;
-    p.batch = 1; p.splitk = 1; p.accumulate = 1;
+    GemmParams p = from_desc(flat_desc(A, lda, W, ldw, C, ldc, ADVGRPO_F32, M, N, K, nullptr, 0, alpha, nullptr, 0, 0, nullptr, 0));
+    p.accumulate = 1;   // this entry alone
     return gemm_bf16(p, as_stream(stream));
+}
+
+// The fields every 3x3 convolution entry sets: x NHWC with `channels` per pixel, w [Cout, K] with K = taps x channels of one weight row,
+// y [B Hout Wout, Cout]; stride 1, no upsample, alpha 1 unless the entry says otherwise.
+static GemmParams conv_params(const void* x, const void* w, void* y, int out_dtype, int B, int Hout, int Wout, int channels, int Cout,
+                              int64_t K, const void* bias, int act, const void* residual, const void* zero_page) {
+    GemmParams p{};
+    p.A = (const bf16_t*)x; p.W = (const bf16_t*)w; p.C = y;
+    p.lda = channels; p.ldw = K; p.ldc = Cout; p.out_dtype = out_dtype;
+    p.M = B * Hout * Wout; p.N = Cout; p.K = (int)K;
+    p.bias = (const bf16_t*)bias; p.act = act; p.alpha = 1.0f;
+    p.residual = (const bf16_t*)residual; p.ldr = Cout;
+    p.batch = 1; p.splitk = 1;
+    p.conv = 1; p.Hout = Hout; p.Wout = Wout; p.Cin = channels;
+    p.zero_page = (const bf16_t*)zero_page;
+    return p;
 }
 
 /* implicit-GEMM conv3x3 (stride 1, pad 1) over NHWC bf16, optional fused nearest-x2 upsample of the input */
 extern "C" int advgrpo_conv3x3_nhwc(const void* x, const void* w, void* y, int out_dtype, int B, int Hout, int Wout,
                                     int Cin, int Cout, int upsample, const void* bias, int act, const void* residual,
                                     const void* zero_page, void* stream) {
-    GemmParams p{};
-    p.A = (const bf16_t*)x; p.W = (const bf16_t*)w; p.C = y;
-    p.lda = Cin; p.ldw = 9 * (int64_t)Cin; p.ldc = Cout; p.out_dtype = out_dtype;
-    p.M = B * Hout * Wout; p.N = Cout; p.K = 9 * Cin;
-    p.bias = (const bf16_t*)bias; p.act = act; p.alpha = 1.0f;
-    p.residual = (const bf16_t*)residual; p.ldr = Cout;
-    p.batch = 1;
-    p.conv = 1; p.Hout = Hout; p.Wout = Wout; p.Cin = Cin; p.ups = upsample ? 1 : 0;
-    p.zero_page = (const bf16_t*)zero_page;
-    p.splitk = 1;
+    GemmParams p = conv_params(x, w, y, out_dtype, B, Hout, Wout, Cin, Cout, 9 * (int64_t)Cin, bias, act, residual, zero_page);
+    p.ups = upsample ? 1 : 0;
     return gemm_bf16(p, as_stream(stream));
 }
 
@@ -519,17 +531,11 @@ static int conv3x3_two_products(const void* x2, const void* w16, float* y, int B
                                 int upsample, const float* bias, int act, const float* residual, const void* zero_page,
                                 float alpha, float* gn_partial, void* stream, int form, void* pair_out = nullptr,
                                 float pair_prescale = 1.0f) {
-    GemmParams p{};
-    p.A = (const bf16_t*)x2; p.W = (const bf16_t*)w16; p.C = y;
-    p.lda = Cin3; p.ldw = 3 * (int64_t)Cin3; p.ldc = Cout; p.out_dtype = ADVGRPO_F32;      // weights [Cout, 9 C], C = Cin3 / 3
-    p.M = B * Hout * Wout; p.N = Cout; p.K = 3 * Cin3;
-    p.bias = (const bf16_t*)bias; p.act = act; p.alpha = alpha;
-    p.residual = (const bf16_t*)residual; p.ldr = Cout;
-    p.batch = 1;
-    p.conv = 1; p.Hout = Hout; p.Wout = Wout; p.Cin = Cin3; p.ups = upsample ? 1 : 0;
-    p.zero_page = (const bf16_t*)zero_page;
-    p.splitk = 1;
+    // weights [Cout, 9 C], C = Cin3 / 3
+    GemmParams p = conv_params(x2, w16, y, ADVGRPO_F32, B, Hout, Wout, Cin3, Cout, 3 * (int64_t)Cin3, bias, act, residual, zero_page);
+    p.ups = upsample ? 1 : 0;
     p.f32_io = 1;
+    p.alpha = alpha;
     p.gn_partial = gn_partial;
     p.pair_out = pair_out; p.pair_prescale = pair_prescale;
     ADVGRPO_CHECK(!pair_out || (!gn_partial && Cout % 4 == 0 && (reinterpret_cast<uintptr_t>(pair_out) & 7) == 0),
@@ -577,16 +583,8 @@ extern "C" int advgrpo_conv3x3_nhwc_bf16x2(const void* x2, const void* w16, floa
 extern "C" int advgrpo_conv3x3_nhwc_x3(const void* x3, const void* w3, float* y, int B, int Hout, int Wout, int Cin3,
                                        int Cout, int upsample, const float* bias, int act, const float* residual,
                                        const void* zero_page, void* stream) {
-    GemmParams p{};
-    p.A = (const bf16_t*)x3; p.W = (const bf16_t*)w3; p.C = y;
-    p.lda = Cin3; p.ldw = 9 * (int64_t)Cin3; p.ldc = Cout; p.out_dtype = ADVGRPO_F32;
-    p.M = B * Hout * Wout; p.N = Cout; p.K = 9 * Cin3;
-    p.bias = (const bf16_t*)bias; p.act = act; p.alpha = 1.0f;
-    p.residual = (const bf16_t*)residual; p.ldr = Cout;
-    p.batch = 1;
-    p.conv = 1; p.Hout = Hout; p.Wout = Wout; p.Cin = Cin3; p.ups = upsample ? 1 : 0;
-    p.zero_page = (const bf16_t*)zero_page;
-    p.splitk = 1;
+    GemmParams p = conv_params(x3, w3, y, ADVGRPO_F32, B, Hout, Wout, Cin3, Cout, 9 * (int64_t)Cin3, bias, act, residual, zero_page);
+    p.ups = upsample ? 1 : 0;
     p.f32_io = 1;
     ADVGRPO_CHECK(Cin3 % 192 == 0, "conv3x3_x3: Cin3 must be 3 x (a multiple of 64) (Cin3=%d)", Cin3);
     // wide outputs: the dedicated kernel (conv_x3.hip: the four hi / lo pieces staged once per 64 channels, three MFMA
@@ -603,16 +601,8 @@ extern "C" int advgrpo_conv3x3_s2_nhwc_x3(const void* x3, const void* w3, float*
     ADVGRPO_CHECK(B > 0 && Hout > 0 && Wout > 0 && (int64_t)B * Hout * Wout < (1ll << 31), "conv3x3_s2_x3: bad shape (B=%d Hout=%d Wout=%d)", B, Hout, Wout);
     ADVGRPO_CHECK(Cin3 > 0 && Cin3 % 192 == 0 && Cout >= 128 && Cout % 4 == 0,
                   "conv3x3_s2_x3: Cin3 must be 3 x (a multiple of 64), Cout >= 128 and a multiple of 4 (Cin3=%d Cout=%d)", Cin3, Cout);
-    GemmParams p{};
-    p.A = (const bf16_t*)x3; p.W = (const bf16_t*)w3; p.C = y;
-    p.lda = Cin3; p.ldw = 9 * (int64_t)Cin3; p.ldc = Cout; p.out_dtype = ADVGRPO_F32;
-    p.M = B * Hout * Wout; p.N = Cout; p.K = 9 * Cin3;
-    p.bias = (const bf16_t*)bias; p.act = 0; p.alpha = 1.0f;
-    p.ldr = Cout;
-    p.batch = 1;
-    p.conv = 1; p.Hout = Hout; p.Wout = Wout; p.Cin = Cin3; p.ups = 0; p.stride2 = 1;
-    p.zero_page = (const bf16_t*)zero_page;
-    p.splitk = 1;
+    GemmParams p = conv_params(x3, w3, y, ADVGRPO_F32, B, Hout, Wout, Cin3, Cout, 9 * (int64_t)Cin3, bias, 0, nullptr, zero_page);
+    p.stride2 = 1;
     p.f32_io = 1;
     return conv3x3_x3_launch(p, as_stream(stream));
 }

@@ -391,47 +391,78 @@ __global__ void unpatchify_kernel(const bf16_t* __restrict__ tok, void* __restri
 
 using namespace advgrpo;
 
-extern "C" int advgrpo_layernorm_mod(const void* x, int64_t ldx, void* out0, void* out1, int64_t ldo, const void* w,
-                                     const void* b, const void* scale0, const void* shift0, const void* scale1,
-                                     const void* shift1, int64_t mod_stride, int rows_per_batch, int M, int D,
-                                     float eps, void* stream) {
-    ADVGRPO_CHECK(x && out0, "layernorm_mod: null pointer");
-    ADVGRPO_CHECK(M > 0 && D > 0 && D % 8 == 0 && D <= LN_MAX_CHUNKS * 512, "layernorm_mod: need D %% 8 == 0, D <= %d (D=%d)",
-                  LN_MAX_CHUNKS * 512, D);
-    ADVGRPO_CHECK(ldx % 8 == 0 && ldo % 8 == 0 && mod_stride % 8 == 0, "layernorm_mod: pitches must be multiples of 8");
-    ADVGRPO_CHECK((scale0 == nullptr) == (shift0 == nullptr), "layernorm_mod: scale0/shift0 come together");
-    ADVGRPO_CHECK(!out1 || (scale1 && shift1), "layernorm_mod: out1 needs scale1/shift1");
-    LnParams p{(const bf16_t*)x, ldx, (bf16_t*)out0, (bf16_t*)out1, ldo, (const bf16_t*)w, (const bf16_t*)b,
-               (const bf16_t*)scale0, (const bf16_t*)shift0, (const bf16_t*)scale1, (const bf16_t*)shift1,
-               mod_stride, rows_per_batch, M, D, eps, 0, nullptr, nullptr, nullptr, nullptr, 0};
-    if (D <= 2048) hipLaunchKernelGGL(layernorm_mod_kernel<4>, dim3((M + 3) / 4), dim3(256), 0, as_stream(stream), p);
-    else hipLaunchKernelGGL(layernorm_mod_kernel<8>, dim3((M + 3) / 4), dim3(256), 0, as_stream(stream), p);
+// Which entry a descriptor came through.  The three copies of the argument checks had drifted apart before they were merged into
+// ln_params; each entry keeps the refusals and texts it had (tests/test_param_block_refusals_host.py pins them):
+//   LN_DESC (advgrpo_layernorm_mod_pair)    x and one of out0 / q0; "a second output needs scale1/shift1"; "q0 needs qs0 and ldq >= D";
+//                                           "q1 needs q0 and qs1"
+//   LN_FLAT (advgrpo_layernorm_mod, advgrpo_rmsnorm_rows: no fp8 fields)    the same conditions, but "out1 needs scale1/shift1"
+//   LN_FLAT_FP8 (advgrpo_layernorm_mod_fp8) x, q0 AND qs0, else "null pointer"; ldq < D is reported with the pitches; "q1 needs qs1"
+enum LnEntry { LN_DESC, LN_FLAT, LN_FLAT_FP8 };
+
+static int ln_params(const advgrpo_ln_desc& d, const char* who, LnParams& p, bool& fp8, LnEntry entry = LN_DESC) {
+    const bool flat8 = entry == LN_FLAT_FP8;
+    ADVGRPO_CHECK(d.x && (flat8 ? d.q0 && d.qs0 : d.out0 || d.q0), "%s: null pointer", who);
+    ADVGRPO_CHECK(d.M > 0 && d.D > 0 && d.D % 8 == 0 && d.D <= LN_MAX_CHUNKS * 512, "%s: need D %% 8 == 0, D <= %d (D=%d)", who,
+                  LN_MAX_CHUNKS * 512, d.D);
+    ADVGRPO_CHECK(d.ldx % 8 == 0 && d.ldo % 8 == 0 && d.mod_stride % 8 == 0 && d.ldq % 8 == 0 && (!flat8 || d.ldq >= d.D),
+                  "%s: pitches must be multiples of 8", who);
+    ADVGRPO_CHECK((d.scale0 == nullptr) == (d.shift0 == nullptr), "%s: scale0/shift0 come together", who);
+    ADVGRPO_CHECK(!(d.out1 || d.q1) || (d.scale1 && d.shift1),
+                  entry == LN_FLAT ? "%s: out1 needs scale1/shift1" : "%s: a second output needs scale1/shift1", who);
+    ADVGRPO_CHECK(!d.q0 || (d.qs0 && d.ldq >= d.D), "%s: q0 needs qs0 and ldq >= D", who);
+    ADVGRPO_CHECK(!d.q1 || (d.q0 && d.qs1), flat8 ? "%s: q1 needs qs1" : "%s: q1 needs q0 and qs1", who);
+    p = {};
+    p.x = (const bf16_t*)d.x; p.ldx = d.ldx;
+    p.out0 = (bf16_t*)d.out0; p.out1 = (bf16_t*)d.out1; p.ldo = d.ldo;
+    p.w = (const bf16_t*)d.w; p.b = (const bf16_t*)d.b;
+    p.scale0 = (const bf16_t*)d.scale0; p.shift0 = (const bf16_t*)d.shift0;
+    p.scale1 = (const bf16_t*)d.scale1; p.shift1 = (const bf16_t*)d.shift1;
+    p.mod_stride = d.mod_stride; p.rows_per_batch = d.rows_per_batch;
+    p.M = d.M; p.D = d.D; p.eps = d.eps;
+    p.q0 = (uint8_t*)d.q0; p.q1 = (uint8_t*)d.q1; p.qs0 = d.qs0; p.qs1 = d.qs1; p.ldq = d.ldq;
+    fp8 = d.q0 != nullptr;
+    return 0;
+}
+
+// the flat entries' arguments as a descriptor (advgrpo_ln_desc lists its fields in their order)
+static advgrpo_ln_desc ln_flat_desc(const void* x, int64_t ldx, void* out0, void* out1, int64_t ldo, const void* w, const void* b,
+                                    const void* scale0, const void* shift0, const void* scale1, const void* shift1, int64_t mod_stride,
+                                    int rows_per_batch, int M, int D, float eps) {
+    advgrpo_ln_desc d{};
+    d.x = x; d.ldx = ldx; d.out0 = out0; d.out1 = out1; d.ldo = ldo; d.w = w; d.b = b;
+    d.scale0 = scale0; d.shift0 = shift0; d.scale1 = scale1; d.shift1 = shift1;
+    d.mod_stride = mod_stride; d.rows_per_batch = rows_per_batch; d.M = M; d.D = D; d.eps = eps;
+    return d;
+}
+
+// one bf16 problem, one launch: four rows per workgroup, the kernel width by D
+static int ln_launch(const LnParams& p, void* stream) {
+    if (p.D <= 2048) hipLaunchKernelGGL(layernorm_mod_kernel<4>, dim3((p.M + 3) / 4), dim3(256), 0, as_stream(stream), p);
+    else hipLaunchKernelGGL(layernorm_mod_kernel<8>, dim3((p.M + 3) / 4), dim3(256), 0, as_stream(stream), p);
     ADVGRPO_LAUNCH_CHECK();
     return 0;
 }
 
-static int ln_from_desc(const advgrpo_ln_desc* d, LnParams& p, bool& fp8) {
-    ADVGRPO_CHECK(d && d->x && (d->out0 || d->q0), "layernorm_mod_pair: null pointer");
-    ADVGRPO_CHECK(d->M > 0 && d->D > 0 && d->D % 8 == 0 && d->D <= LN_MAX_CHUNKS * 512, "layernorm_mod_pair: need D %% 8 == 0, D <= %d (D=%d)",
-                  LN_MAX_CHUNKS * 512, d->D);
-    ADVGRPO_CHECK(d->ldx % 8 == 0 && d->ldo % 8 == 0 && d->mod_stride % 8 == 0 && d->ldq % 8 == 0, "layernorm_mod_pair: pitches must be multiples of 8");
-    ADVGRPO_CHECK((d->scale0 == nullptr) == (d->shift0 == nullptr), "layernorm_mod_pair: scale0/shift0 come together");
-    ADVGRPO_CHECK(!(d->out1 || d->q1) || (d->scale1 && d->shift1), "layernorm_mod_pair: a second output needs scale1/shift1");
-    ADVGRPO_CHECK(!d->q0 || (d->qs0 && d->ldq >= d->D), "layernorm_mod_pair: q0 needs qs0 and ldq >= D");
-    ADVGRPO_CHECK(!d->q1 || (d->q0 && d->qs1), "layernorm_mod_pair: q1 needs q0 and qs1");
-    p = LnParams{(const bf16_t*)d->x, d->ldx, (bf16_t*)d->out0, (bf16_t*)d->out1, d->ldo, (const bf16_t*)d->w, (const bf16_t*)d->b,
-                 (const bf16_t*)d->scale0, (const bf16_t*)d->shift0, (const bf16_t*)d->scale1, (const bf16_t*)d->shift1,
-                 d->mod_stride, d->rows_per_batch, d->M, d->D, d->eps, 0, (uint8_t*)d->q0, (uint8_t*)d->q1, d->qs0, d->qs1, d->ldq};
-    fp8 = d->q0 != nullptr;
-    return 0;
+extern "C" int advgrpo_layernorm_mod(const void* x, int64_t ldx, void* out0, void* out1, int64_t ldo, const void* w,
+                                     const void* b, const void* scale0, const void* shift0, const void* scale1,
+                                     const void* shift1, int64_t mod_stride, int rows_per_batch, int M, int D,
+                                     float eps, void* stream) {
+    LnParams p;
+    bool fp8;
+    if (int rc = ln_params(ln_flat_desc(x, ldx, out0, out1, ldo, w, b, scale0, shift0, scale1, shift1, mod_stride, rows_per_batch, M, D, eps),
+                           "layernorm_mod", p, fp8, LN_FLAT))
+        return rc;
+    return ln_launch(p, stream);
 }
 
 /* Two advgrpo_layernorm_mod / _fp8 problems in one launch (the image-stream and text-stream norms of an MMDiT block). */
 extern "C" int advgrpo_layernorm_mod_pair(const advgrpo_ln_desc* a, const advgrpo_ln_desc* b, void* stream) {
     LnPair pp{};
     bool fa = false, fb = false;
-    if (int rc = ln_from_desc(a, pp.a, fa)) return rc;
-    if (int rc = ln_from_desc(b, pp.b, fb)) return rc;
+    ADVGRPO_CHECK(a, "layernorm_mod_pair: null pointer");
+    if (int rc = ln_params(*a, "layernorm_mod_pair", pp.a, fa)) return rc;
+    ADVGRPO_CHECK(b, "layernorm_mod_pair: null pointer");
+    if (int rc = ln_params(*b, "layernorm_mod_pair", pp.b, fb)) return rc;
     ADVGRPO_CHECK(fa == fb, "layernorm_mod_pair: both problems bf16 or both fp8");
     pp.blocks_a = (pp.a.M + 3) / 4;
     const dim3 grid(pp.blocks_a + (pp.b.M + 3) / 4);
@@ -454,17 +485,11 @@ extern "C" int advgrpo_layernorm_mod_fp8(const void* x, int64_t ldx, void* out0,
                                          const void* b, const void* scale0, const void* shift0, const void* scale1,
                                          const void* shift1, int64_t mod_stride, int rows_per_batch, int M, int D, float eps,
                                          void* q0, float* qs0, void* q1, float* qs1, int64_t ldq, void* stream) {
-    ADVGRPO_CHECK(x && q0 && qs0, "layernorm_mod_fp8: null pointer");
-    ADVGRPO_CHECK(M > 0 && D > 0 && D % 8 == 0 && D <= LN_MAX_CHUNKS * 512, "layernorm_mod_fp8: need D %% 8 == 0, D <= %d (D=%d)",
-                  LN_MAX_CHUNKS * 512, D);
-    ADVGRPO_CHECK(ldx % 8 == 0 && ldo % 8 == 0 && mod_stride % 8 == 0 && ldq % 8 == 0 && ldq >= D,
-                  "layernorm_mod_fp8: pitches must be multiples of 8");
-    ADVGRPO_CHECK((scale0 == nullptr) == (shift0 == nullptr), "layernorm_mod_fp8: scale0/shift0 come together");
-    ADVGRPO_CHECK(!(out1 || q1) || (scale1 && shift1), "layernorm_mod_fp8: a second output needs scale1/shift1");
-    ADVGRPO_CHECK(!q1 || qs1, "layernorm_mod_fp8: q1 needs qs1");
-    LnParams p{(const bf16_t*)x, ldx, (bf16_t*)out0, (bf16_t*)out1, ldo, (const bf16_t*)w, (const bf16_t*)b,
-               (const bf16_t*)scale0, (const bf16_t*)shift0, (const bf16_t*)scale1, (const bf16_t*)shift1,
-               mod_stride, rows_per_batch, M, D, eps, 0, (uint8_t*)q0, (uint8_t*)q1, qs0, qs1, ldq};
+    advgrpo_ln_desc d = ln_flat_desc(x, ldx, out0, out1, ldo, w, b, scale0, shift0, scale1, shift1, mod_stride, rows_per_batch, M, D, eps);
+    d.q0 = q0; d.qs0 = qs0; d.q1 = q1; d.qs1 = qs1; d.ldq = ldq;
+    LnParams p;
+    bool fp8;
+    if (int rc = ln_params(d, "layernorm_mod_fp8", p, fp8, LN_FLAT_FP8)) return rc;
     if (D <= 2048) hipLaunchKernelGGL((layernorm_mod_kernel<4, true>), dim3((M + 3) / 4), dim3(256), 0, as_stream(stream), p);
     else hipLaunchKernelGGL((layernorm_mod_kernel<8, true>), dim3((M + 3) / 4), dim3(256), 0, as_stream(stream), p);
     ADVGRPO_LAUNCH_CHECK();
@@ -476,15 +501,13 @@ extern "C" int advgrpo_layernorm_mod_fp8(const void* x, int64_t ldx, void* out0,
 extern "C" int advgrpo_rmsnorm_rows(const void* x, int64_t ldx, void* out, int64_t ldo, const void* w, int M, int D, float eps,
                                     void* stream) {
     ADVGRPO_CHECK(x && out && w, "rmsnorm_rows: null pointer");
-    ADVGRPO_CHECK(M > 0 && D > 0 && D % 8 == 0 && D <= LN_MAX_CHUNKS * 512, "rmsnorm_rows: need D %% 8 == 0, D <= %d (D=%d)",
-                  LN_MAX_CHUNKS * 512, D);
-    ADVGRPO_CHECK(ldx % 8 == 0 && ldo % 8 == 0, "rmsnorm_rows: pitches must be multiples of 8");
-    LnParams p{(const bf16_t*)x, ldx, (bf16_t*)out, nullptr, ldo, (const bf16_t*)w, nullptr, nullptr, nullptr, nullptr, nullptr,
-               0, 0, M, D, eps, 1};
-    if (D <= 2048) hipLaunchKernelGGL(layernorm_mod_kernel<4>, dim3((M + 3) / 4), dim3(256), 0, as_stream(stream), p);
-    else hipLaunchKernelGGL(layernorm_mod_kernel<8>, dim3((M + 3) / 4), dim3(256), 0, as_stream(stream), p);
-    ADVGRPO_LAUNCH_CHECK();
-    return 0;
+    LnParams p;
+    bool fp8;
+    if (int rc = ln_params(ln_flat_desc(x, ldx, out, nullptr, ldo, w, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, M, D, eps),
+                           "rmsnorm_rows", p, fp8, LN_FLAT))
+        return rc;
+    p.rms = 1;   // no mean subtraction, the weight multiplies the bf16-rounded value
+    return ln_launch(p, stream);
 }
 
 extern "C" int advgrpo_rmsnorm_heads(void* buf, int64_t ld, int M, int col0, int nheads, const void* weight,

@@ -2,7 +2,6 @@
 
 Host plumbing only: allocation via torch, pointers + sizes handed to libadvgrpo_hip.so."""
 import ctypes
-
 import threading
 
 import torch
@@ -10,6 +9,7 @@ import torch
 from . import _lib
 
 ACT = {None: 0, "none": 0, "gelu_tanh": 1, "gelu_new": 1, "gelu": 2, "gelu_erf": 2, "silu": 3, "quick_gelu": 4}
+ACT_D = {"dgelu_tanh": 5, "dgelu": 6, "mul_aux": 7}   # training epilogues on aux_in; "mul_aux": y *= aux_in (gated feed-forward)
 
 GEMM_VARIANTS = {0: "gemm_bf16_kernel<128,128,2,2,false>", 1: "gemm_bf16_kernel<128,64,2,2,false>",
                  2: "gemm_bf16_kernel<64,128,2,2,false>", 4: "gemm_bf16_kernel<128,128,2,2,true>",
@@ -50,15 +50,15 @@ class _Prof:
             PROFILE.append((self.name, self.flops, self.s, self.e, self.shape))
 
 
-def gemm(a, w, bias=None, act=None, alpha=1.0, gate=None, gate_rows=0, residual=None, out=None,
-         out_dtype=torch.bfloat16, seg=None, a_seg=None, M=None):
-    """out[M,N] = epilogue(a[M,K] @ w[N,K]^T).  a, w: bf16, last dim contiguous.
-    gate: [G, N] bf16 with row m using gate[m // gate_rows].  residual: [rows, N] bf16 (indexed with the
-    output row map).  seg = (seg_rows, seg_stride, seg_off) scatters row m to
-    (m // seg_rows) * seg_stride + seg_off + m % seg_rows of `out` (which must then be given)."""
-    lib = _lib.load()
+def _dp(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _linear(a, w, out, out_dtype, seg, a_seg, M, act, aux_out=None, aux_in=None):
+    """What gemm, gemm_desc and gemm_train share: the operand checks, M / N / K, the output (allocated unless given), the two row maps
+    as int triples, the activation code and the aux pitch."""
     assert a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
-    assert a.dim() == 2 and w.dim() == 2 and a.shape[1] == w.shape[1]
+    assert len(a.shape) == 2 and len(w.shape) == 2 and a.shape[1] == w.shape[1]
     assert a.stride(1) == 1 and w.stride(1) == 1
     K = a.shape[1]
     M = a.shape[0] if M is None else M
@@ -67,16 +67,26 @@ def gemm(a, w, bias=None, act=None, alpha=1.0, gate=None, gate_rows=0, residual=
         assert seg is None
         out = torch.empty(M, N, dtype=out_dtype, device=a.device)
     assert out.stride(-1) == 1
-    seg_rows, seg_stride, seg_off = seg if seg is not None else (0, 0, 0)
-    a_rows, a_stride, a_off = a_seg if a_seg is not None else (0, 0, 0)
+    seg = tuple(int(v) for v in seg) if seg is not None else (0, 0, 0)
+    a_seg = tuple(int(v) for v in a_seg) if a_seg is not None else (0, 0, 0)
+    aux = aux_out if aux_out is not None else aux_in
+    return M, N, K, out, seg, a_seg, ACT_D[act] if act in ACT_D else ACT[act], aux.stride(0) if aux is not None else 0
+
+
+def gemm(a, w, bias=None, act=None, alpha=1.0, gate=None, gate_rows=0, residual=None, out=None,
+         out_dtype=torch.bfloat16, seg=None, a_seg=None, M=None):
+    """out[M,N] = epilogue(a[M,K] @ w[N,K]^T).  a, w: bf16, last dim contiguous.
+    gate: [G, N] bf16 with row m using gate[m // gate_rows].  residual: [rows, N] bf16 (indexed with the
+    output row map).  seg = (seg_rows, seg_stride, seg_off) scatters row m to
+    (m // seg_rows) * seg_stride + seg_off + m % seg_rows of `out` (which must then be given)."""
+    lib = _lib.load()
+    M, N, K, out, seg, a_seg, code, _ = _linear(a, w, out, out_dtype, seg, a_seg, M, act)
     with _Prof(M, N, K, 1, 0):
-      _lib.check(lib.advgrpo_gemm_bf16(
-        a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(-2),
-        _lib.dtype_code(out.dtype), M, N, K, _lib.ptr(bias), ACT[act], float(alpha),
-        gate.data_ptr() if gate is not None else None, gate.stride(0) if gate is not None else 0, int(gate_rows),
-        residual.data_ptr() if residual is not None else None, residual.stride(-2) if residual is not None else 0,
-        int(seg_rows), int(seg_stride), int(seg_off), int(a_rows), int(a_stride), int(a_off), 1, 0, 0, 0,
-        _lib.stream_ptr()))
+        _lib.check(lib.advgrpo_gemm_bf16(
+            a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(-2),
+            _lib.dtype_code(out.dtype), M, N, K, _lib.ptr(bias), code, float(alpha),
+            _dp(gate), gate.stride(0) if gate is not None else 0, int(gate_rows),
+            _dp(residual), residual.stride(-2) if residual is not None else 0, *seg, *a_seg, 1, 0, 0, 0, _lib.stream_ptr()))
     return out
 
 
@@ -85,39 +95,23 @@ def gemm_desc(a, w, bias=None, act=None, alpha=1.0, gate=None, gate_rows=0, resi
     """Descriptor of one Linear for gemm_grouped (arguments as in gemm / gemm_train).
     rms = (weight [n_w, 64] bf16, nheads, heads_per_weight, eps, rs_out or None): fused per-head RMSNorm of the first
     `nheads` 64-wide output column groups (QK-norm of a fused QKV projection).  Returns (descriptor, out)."""
-    assert a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and a.shape[1] == w.shape[1]
-    assert a.stride(1) == 1 and w.stride(1) == 1
-    K = a.shape[1]
-    M = a.shape[0] if M is None else M
-    N = w.shape[0]
-    if out is None:
-        assert seg is None
-        out = torch.empty(M, N, dtype=out_dtype, device=a.device)
-    assert out.stride(-1) == 1
+    M, N, K, out, seg, a_seg, code, ld_aux = _linear(a, w, out, out_dtype, seg, a_seg, M, act, aux_out, aux_in)
     d = _lib.GemmDesc()
     d.A, d.W, d.C = a.data_ptr(), w.data_ptr(), out.data_ptr()
     d.lda, d.ldw, d.ldc = a.stride(0), w.stride(0), out.stride(-2)
     d.out_dtype, d.M, d.N, d.K = _lib.dtype_code(out.dtype), M, N, K
-    d.bias = bias.data_ptr() if bias is not None else None
-    d.act = ACT_D[act] if act in ACT_D else ACT[act]
-    d.alpha = float(alpha)
+    d.bias, d.act, d.alpha = _dp(bias), code, float(alpha)
     if gate is not None:
         d.gate, d.gate_stride, d.gate_rows = gate.data_ptr(), gate.stride(0), int(gate_rows)
     if residual is not None:
         d.residual, d.ldr = residual.data_ptr(), residual.stride(-2)
-    if seg is not None:
-        d.seg_rows, d.seg_stride, d.seg_off = (int(v) for v in seg)
-    if a_seg is not None:
-        d.a_seg_rows, d.a_seg_stride, d.a_seg_off = (int(v) for v in a_seg)
-    aux = aux_out if aux_out is not None else aux_in
-    if aux is not None:
-        d.aux_out = aux_out.data_ptr() if aux_out is not None else None
-        d.aux_in = aux_in.data_ptr() if aux_in is not None else None
-        d.ld_aux = aux.stride(0)
+    d.seg_rows, d.seg_stride, d.seg_off = seg
+    d.a_seg_rows, d.a_seg_stride, d.a_seg_off = a_seg
+    d.aux_out, d.aux_in, d.ld_aux = _dp(aux_out), _dp(aux_in), ld_aux
     if rms is not None:
         rw, nheads, hpw, eps, rs_out = rms
         d.rms_weight, d.rms_nheads, d.rms_heads_per_weight, d.rms_eps = rw.data_ptr(), int(nheads), int(hpw), float(eps)
-        d.rms_rs_out = rs_out.data_ptr() if rs_out is not None else None
+        d.rms_rs_out = _dp(rs_out)
     return d, out
 
 
@@ -221,10 +215,10 @@ def bmm_nt(a, w, out=None, out_dtype=torch.bfloat16, alpha=1.0):
     if out is None:
         out = torch.empty(B, M, N, dtype=out_dtype, device=a.device)
     with _Prof(M, N, K, B, 0):
-      _lib.check(lib.advgrpo_gemm_bf16(
-        a.data_ptr(), a.stride(1), w.data_ptr(), w.stride(1), out.data_ptr(), out.stride(1),
-        _lib.dtype_code(out.dtype), M, N, K, None, 0, float(alpha), None, 0, 0, None, 0, 0, 0, 0, 0, 0, 0,
-        B, a.stride(0), w.stride(0), out.stride(0), _lib.stream_ptr()))
+        _lib.check(lib.advgrpo_gemm_bf16(
+            a.data_ptr(), a.stride(1), w.data_ptr(), w.stride(1), out.data_ptr(), out.stride(1),
+            _lib.dtype_code(out.dtype), M, N, K, None, 0, float(alpha), None, 0, 0, None, 0, 0, 0, 0, 0, 0, 0,
+            B, a.stride(0), w.stride(0), out.stride(0), _lib.stream_ptr()))
     return out
 
 
@@ -288,87 +282,57 @@ def attention_bwd(q, k, v, o, d_o, lse, num_heads, dq, dk, dv, scale=None):
     return dq, dk, dv
 
 
-def layernorm_mod(x, out=None, w=None, b=None, scale=None, shift=None, scale2=None, shift2=None,
-                  rows_per_batch=0, eps=1e-6):
-    """x [M,D] bf16.  scale/shift [Bt,D] views (row pitch = stride(0)); returns out (and out2 if scale2 given)."""
-    lib = _lib.load()
+def _ln_fields(x, out=None, out2=None, w=None, b=None, scale=None, shift=None, scale2=None, shift2=None, rows_per_batch=0, eps=1e-6,
+               q=None, q2=None):
+    """One LayerNorm problem -> (the fields of _lib.LnDesc in their order, the value to return).  That order is also the argument order
+    of the flat C entries: advgrpo_layernorm_mod takes the first 16, advgrpo_layernorm_mod_fp8 all of them.  q (/ q2): Fp8Rows, the
+    fp8 form -- then out / out2 are optional; without it they are allocated here unless given."""
     M, D = x.shape
-    out = torch.empty(M, D, dtype=torch.bfloat16, device=x.device) if out is None else out
-    # (out2 shares out's row pitch: one ldo for both in the C entry)
-    out2 = torch.empty_strided(out.shape, out.stride(), dtype=out.dtype, device=out.device) if scale2 is not None else None
-    ms = scale.stride(0) if scale is not None else 0
-    if scale is not None:
-        assert shift.stride(0) == ms and scale.stride(1) == 1
-    if scale2 is not None:
-        assert scale2.stride(0) == ms and shift2.stride(0) == ms
-    dp = lambda t: t.data_ptr() if t is not None else None
-    _lib.check(lib.advgrpo_layernorm_mod(x.data_ptr(), x.stride(0), out.data_ptr(), dp(out2), out.stride(0), dp(w),
-                                         dp(b), dp(scale), dp(shift), dp(scale2), dp(shift2), ms, int(rows_per_batch),
-                                         M, D, float(eps), _lib.stream_ptr()))
-    return (out, out2) if scale2 is not None else out
-
-
-def layernorm_mod_fp8(x, q, q2=None, out=None, out2=None, w=None, b=None, scale=None, shift=None, scale2=None, shift2=None,
-                      rows_per_batch=0, eps=1e-6):
-    """layernorm_mod whose output(s) leave as fp8 rows (q, q2: Fp8Rows of M rows) for the fp8 Linears; out / out2: the bf16
-    tensors to write as well, or None to skip them.  The codes equal quant_fp8_rows(layernorm_mod(...)) bit for bit."""
-    lib = _lib.load()
-    M, D = x.shape
-    assert q.q.shape == (M, D) and q.q.stride(1) == 1 and q.scale.numel() == M and (q2 is None) == (scale2 is None)
-    assert q2 is None or (q2.q.shape == (M, D) and q2.q.stride(0) == q.q.stride(0))
+    fp8 = q is not None
+    if not fp8:
+        out = torch.empty(M, D, dtype=torch.bfloat16, device=x.device) if out is None else out
+        if scale2 is not None and out2 is None:       # (out2 shares out's row pitch: one ldo for both in the C entry)
+            out2 = torch.empty_strided(out.shape, out.stride(), dtype=out.dtype, device=out.device)
+    else:
+        assert q.q.shape == (M, D) and q.q.stride(1) == 1 and q.scale.numel() == M and (q2 is None) == (scale2 is None)
+        assert q2 is None or (q2.q.shape == (M, D) and q2.q.stride(0) == q.q.stride(0))
     assert out2 is None or (out is not None and out2.stride() == out.stride())
     ms = scale.stride(0) if scale is not None else 0
     if scale is not None:
         assert shift.stride(0) == ms and scale.stride(1) == 1
     if scale2 is not None:
         assert scale2.stride(0) == ms and shift2.stride(0) == ms
-    dp = lambda t: t.data_ptr() if t is not None else None
-    _lib.check(lib.advgrpo_layernorm_mod_fp8(x.data_ptr(), x.stride(0), dp(out), dp(out2), out.stride(0) if out is not None else D,
-                                             dp(w), dp(b), dp(scale), dp(shift), dp(scale2), dp(shift2), ms, int(rows_per_batch),
-                                             M, D, float(eps), q.q.data_ptr(), q.scale.data_ptr(),
-                                             q2.q.data_ptr() if q2 is not None else None,
-                                             q2.scale.data_ptr() if q2 is not None else None, q.q.stride(0), _lib.stream_ptr()))
-    return out, out2
+    fields = (x.data_ptr(), x.stride(0), _dp(out), _dp(out2), out.stride(0) if out is not None else D, _dp(w), _dp(b),
+              _dp(scale), _dp(shift), _dp(scale2), _dp(shift2), ms, int(rows_per_batch), M, D, float(eps),
+              q.q.data_ptr() if fp8 else None, q.scale.data_ptr() if fp8 else None,
+              q2.q.data_ptr() if q2 is not None else None, q2.scale.data_ptr() if q2 is not None else None, q.q.stride(0) if fp8 else 0)
+    return fields, (out, out2) if (fp8 or scale2 is not None) else out
+
+
+def layernorm_mod(x, out=None, w=None, b=None, scale=None, shift=None, scale2=None, shift2=None,
+                  rows_per_batch=0, eps=1e-6):
+    """x [M,D] bf16.  scale/shift [Bt,D] views (row pitch = stride(0)); returns out (and out2 if scale2 given)."""
+    fields, ret = _ln_fields(x, out, None, w, b, scale, shift, scale2, shift2, rows_per_batch, eps)
+    _lib.check(_lib.load().advgrpo_layernorm_mod(*fields[:16], _lib.stream_ptr()))
+    return ret
+
+
+def layernorm_mod_fp8(x, q, q2=None, out=None, out2=None, w=None, b=None, scale=None, shift=None, scale2=None, shift2=None,
+                      rows_per_batch=0, eps=1e-6):
+    """layernorm_mod whose output(s) leave as fp8 rows (q, q2: Fp8Rows of M rows) for the fp8 Linears; out / out2: the bf16
+    tensors to write as well, or None to skip them.  The codes equal quant_fp8_rows(layernorm_mod(...)) bit for bit."""
+    fields, ret = _ln_fields(x, out, out2, w, b, scale, shift, scale2, shift2, rows_per_batch, eps, q, q2)
+    _lib.check(_lib.load().advgrpo_layernorm_mod_fp8(*fields, _lib.stream_ptr()))
+    return ret
 
 
 def layernorm_mod_pair(a, b):
     """Two layernorm_mod (or two layernorm_mod_fp8) problems in ONE launch: a, b are dicts of that function's keyword arguments
     plus "x" (and "q" / "q2" for the fp8 form: then "out" / "out2" are optional and may stay None).  Returns the two results in the
     single call's form.  Bit-identical to two calls; saves the launch-bound text-stream launch of an MMDiT block."""
-    lib = _lib.load()
-    descs, keep, rets = [], [], []
-    for kw in (a, b):
-        x = kw["x"]
-        M, D = x.shape
-        fp8 = kw.get("q") is not None
-        scale, shift, scale2, shift2 = kw.get("scale"), kw.get("shift"), kw.get("scale2"), kw.get("shift2")
-        out, out2 = kw.get("out"), kw.get("out2")
-        q, q2 = kw.get("q"), kw.get("q2")
-        if not fp8:
-            out = torch.empty(M, D, dtype=torch.bfloat16, device=x.device) if out is None else out
-            if scale2 is not None and out2 is None:
-                out2 = torch.empty_strided(out.shape, out.stride(), dtype=out.dtype, device=out.device)
-        else:
-            assert q.q.shape == (M, D) and q.q.stride(1) == 1 and q.scale.numel() == M and (q2 is None) == (scale2 is None)
-            assert q2 is None or (q2.q.shape == (M, D) and q2.q.stride(0) == q.q.stride(0))
-        assert out2 is None or (out is not None and out2.stride() == out.stride())
-        ms = scale.stride(0) if scale is not None else 0
-        if scale is not None:
-            assert shift.stride(0) == ms and scale.stride(1) == 1
-        if scale2 is not None:
-            assert scale2.stride(0) == ms and shift2.stride(0) == ms
-        dp = lambda t: t.data_ptr() if t is not None else None
-        d = _lib.LnDesc(x.data_ptr(), x.stride(0), dp(out), dp(out2), out.stride(0) if out is not None else D, dp(kw.get("w")),
-                        dp(kw.get("b")), dp(scale), dp(shift), dp(scale2), dp(shift2), ms, int(kw.get("rows_per_batch", 0)), M, D,
-                        float(kw.get("eps", 1e-6)), q.q.data_ptr() if fp8 else None, q.scale.data_ptr() if fp8 else None,
-                        q2.q.data_ptr() if q2 is not None else None, q2.scale.data_ptr() if q2 is not None else None,
-                        q.q.stride(0) if fp8 else 0)
-        descs.append(d)
-        keep.append((x, out, out2, scale, shift, scale2, shift2, q, q2, kw.get("w"), kw.get("b")))
-        rets.append((out, out2) if (fp8 or scale2 is not None) else out)
-    _lib.check(lib.advgrpo_layernorm_mod_pair(ctypes.byref(descs[0]), ctypes.byref(descs[1]), _lib.stream_ptr()))
-    del keep
-    return rets[0], rets[1]
+    (fa, ra), (fb, rb) = _ln_fields(**a), _ln_fields(**b)
+    _lib.check(_lib.load().advgrpo_layernorm_mod_pair(ctypes.byref(_lib.LnDesc(*fa)), ctypes.byref(_lib.LnDesc(*fb)), _lib.stream_ptr()))
+    return ra, rb
 
 
 def rmsnorm_rows(x, w, eps=1e-6, out=None):
@@ -527,17 +491,30 @@ def zero_page(device):
     return cached(_ZERO_PAGE, str(device), lambda: torch.zeros(256, dtype=torch.bfloat16, device=device))
 
 
+def _conv(x, w, bias, residual, upsample=False, f32=True, stride2=False):
+    """What the 3x3 convolution wrappers share -> (B, Hout, Wout, channels per pixel, Cout, zero page pointer); f32: the split-operand
+    forms, whose bias / residual are f32."""
+    B, Hin, Win, C = x.shape
+    if stride2:
+        assert Hin % 2 == 0 and Win % 2 == 0 and x.dtype == torch.bfloat16
+        Hout, Wout = Hin // 2, Win // 2
+    else:
+        Hout, Wout = (Hin * 2, Win * 2) if upsample else (Hin, Win)
+    if f32:
+        assert bias is None or bias.dtype == torch.float32
+        assert residual is None or (residual.dtype == torch.float32 and residual.is_contiguous())
+    return B, Hout, Wout, C, w.shape[0], zero_page(x.device).data_ptr()
+
+
 def conv3x3(x, w, bias=None, upsample=False, act=None, residual=None, out_dtype=torch.bfloat16):
     """x NHWC bf16 [B,Hin,Win,Cin]; w [Cout, 9*Cin] bf16 (k = (ky*3+kx)*Cin + c) -> [B,Hout,Wout,Cout]."""
     lib = _lib.load()
-    B, Hin, Win, Cin = x.shape
-    Cout = w.shape[0]
-    Hout, Wout = (Hin * 2, Win * 2) if upsample else (Hin, Win)
+    B, Hout, Wout, Cin, Cout, zp = _conv(x, w, bias, residual, upsample, f32=False)
     y = torch.empty(B, Hout, Wout, Cout, dtype=out_dtype, device=x.device)
     with _Prof(B * Hout * Wout, Cout, 9 * Cin, 1, 1):
-      _lib.check(lib.advgrpo_conv3x3_nhwc(_lib.ptr(x), _lib.ptr(w), y.data_ptr(), _lib.dtype_code(out_dtype), B, Hout, Wout,
-                                        Cin, Cout, int(upsample), _lib.ptr(bias), ACT[act], _lib.ptr(residual),
-                                        zero_page(x.device).data_ptr(), _lib.stream_ptr()))
+        _lib.check(lib.advgrpo_conv3x3_nhwc(_lib.ptr(x), _lib.ptr(w), y.data_ptr(), _lib.dtype_code(out_dtype), B, Hout, Wout,
+                                            Cin, Cout, int(upsample), _lib.ptr(bias), ACT[act], _lib.ptr(residual), zp,
+                                            _lib.stream_ptr()))
     return y
 
 
@@ -568,16 +545,11 @@ def split_x3(x, order=0, bias=None):
 def conv3x3_x3(x3, w3, bias=None, upsample=False, act=None, residual=None):
     """x3 NHWC split bf16 [B,Hin,Win,3C]; w3 [Cout, 9*3C]; bias / residual f32 -> f32 [B,Hout,Wout,Cout]."""
     lib = _lib.load()
-    B, Hin, Win, Cin3 = x3.shape
-    Cout = w3.shape[0]
-    Hout, Wout = (Hin * 2, Win * 2) if upsample else (Hin, Win)
-    assert bias is None or bias.dtype == torch.float32
-    assert residual is None or (residual.dtype == torch.float32 and residual.is_contiguous())
+    B, Hout, Wout, Cin3, Cout, zp = _conv(x3, w3, bias, residual, upsample)
     y = torch.empty(B, Hout, Wout, Cout, dtype=torch.float32, device=x3.device)
     with _Prof(B * Hout * Wout, Cout, 9 * Cin3, 1, 1):
-      _lib.check(lib.advgrpo_conv3x3_nhwc_x3(_lib.ptr(x3), _lib.ptr(w3), y.data_ptr(), B, Hout, Wout, Cin3, Cout, int(upsample),
-                                           _lib.ptr(bias), ACT[act], _lib.ptr(residual), zero_page(x3.device).data_ptr(),
-                                           _lib.stream_ptr()))
+        _lib.check(lib.advgrpo_conv3x3_nhwc_x3(_lib.ptr(x3), _lib.ptr(w3), y.data_ptr(), B, Hout, Wout, Cin3, Cout, int(upsample),
+                                               _lib.ptr(bias), ACT[act], _lib.ptr(residual), zp, _lib.stream_ptr()))
     return y
 
 
@@ -585,14 +557,11 @@ def conv3x3_s2_x3(x3, w3, bias=None):
     """Downsample2D(padding=0): F.pad(x, (0, 1, 0, 1)) + 3x3 convolution of stride 2.  x3 NHWC split bf16 [B,Hin,Win,3C] (Hin, Win even; the hi
     and lo thirds are read), w3 [Cout, 9*3C], bias f32 -> f32 [B,Hin/2,Win/2,Cout]."""
     lib = _lib.load()
-    B, Hin, Win, Cin3 = x3.shape
-    assert Hin % 2 == 0 and Win % 2 == 0 and x3.dtype == torch.bfloat16
-    assert bias is None or bias.dtype == torch.float32
-    Cout = w3.shape[0]
-    y = torch.empty(B, Hin // 2, Win // 2, Cout, dtype=torch.float32, device=x3.device)
-    with _Prof(B * (Hin // 2) * (Win // 2), Cout, 9 * Cin3, 1, 1):
-      _lib.check(lib.advgrpo_conv3x3_s2_nhwc_x3(_lib.ptr(x3), _lib.ptr(w3), y.data_ptr(), B, Hin // 2, Win // 2, Cin3, Cout, _lib.ptr(bias),
-                                              zero_page(x3.device).data_ptr(), _lib.stream_ptr()))
+    B, Hout, Wout, Cin3, Cout, zp = _conv(x3, w3, bias, None, stride2=True)
+    y = torch.empty(B, Hout, Wout, Cout, dtype=torch.float32, device=x3.device)
+    with _Prof(B * Hout * Wout, Cout, 9 * Cin3, 1, 1):
+        _lib.check(lib.advgrpo_conv3x3_s2_nhwc_x3(_lib.ptr(x3), _lib.ptr(w3), y.data_ptr(), B, Hout, Wout, Cin3, Cout, _lib.ptr(bias), zp,
+                                                  _lib.stream_ptr()))
     return y
 
 
@@ -716,17 +685,13 @@ def conv3x3_f16x2_pair(x2, w16, prescale, bias=None, upsample=False, act=None, r
     """conv3x3_f16x2 whose output leaves as the fp16-pair rows of prescale * y ([B,Hout,Wout,3 Cout], = split_f16x2(y, prescale) bit for
     bit) instead of f32 y: for an output that only the next f16x2 convolution reads."""
     lib = _lib.load()
-    B, Hin, Win, Cin3 = x2.shape
-    Cout = w16.shape[0]
+    B, Hout, Wout, Cin3, Cout, zp = _conv(x2, w16, bias, residual, upsample)
     assert w16.dtype == torch.float16 and w16.is_contiguous() and w16.shape[1] == 3 * Cin3
-    assert bias is None or bias.dtype == torch.float32
-    assert residual is None or (residual.dtype == torch.float32 and residual.is_contiguous())
-    Hout, Wout = (Hin * 2, Win * 2) if upsample else (Hin, Win)
+    fn = lib.advgrpo_conv3x3_nhwc_f16x1_pair if single else lib.advgrpo_conv3x3_nhwc_f16x2_pair
     out = torch.empty(B, Hout, Wout, 3 * Cout, dtype=torch.bfloat16, device=x2.device)      # (16-bit container; the values are fp16)
     with _Prof(B * Hout * Wout, Cout, 2 * 3 * Cin3, 1, 1):
-        _lib.check((lib.advgrpo_conv3x3_nhwc_f16x1_pair if single else lib.advgrpo_conv3x3_nhwc_f16x2_pair)(_lib.ptr(x2), _lib.ptr(w16), out.data_ptr(), float(prescale), B, Hout, Wout, Cin3, Cout,
-                                                       int(upsample), _lib.ptr(bias), ACT[act], _lib.ptr(residual),
-                                                       zero_page(x2.device).data_ptr(), float(alpha), _lib.stream_ptr()))
+        _lib.check(fn(_lib.ptr(x2), _lib.ptr(w16), out.data_ptr(), float(prescale), B, Hout, Wout, Cin3, Cout, int(upsample),
+                      _lib.ptr(bias), ACT[act], _lib.ptr(residual), zp, float(alpha), _lib.stream_ptr()))
     return out
 
 
@@ -736,23 +701,18 @@ def conv3x3_f16x2(x2, w16, bias=None, upsample=False, act=None, residual=None, a
     gn_stats: the epilogue also leaves the 16-pixel x 4-channel block sums of the GroupNorm that reads the output, as `y.gn_tile_stats` (an attribute
     of THIS tensor object: views do not carry it)."""
     lib = _lib.load()
-    B, Hin, Win, Cin3 = x2.shape
-    Cout = w16.shape[0]
+    B, Hout, Wout, Cin3, Cout, zp = _conv(x2, w16, bias, residual, upsample)
     assert w16.dtype == (torch.bfloat16 if bf16_pieces else torch.float16) and w16.is_contiguous() and w16.shape[1] == 3 * Cin3
     assert not (single and bf16_pieces)
     # single: the TF32-class "f16x1" form (the hi product only; include/advgrpo.h)
     fn = lib.advgrpo_conv3x3_nhwc_bf16x2 if bf16_pieces else (lib.advgrpo_conv3x3_nhwc_f16x1 if single else lib.advgrpo_conv3x3_nhwc_f16x2)
-    Hout, Wout = (Hin * 2, Win * 2) if upsample else (Hin, Win)
-    assert bias is None or bias.dtype == torch.float32
-    assert residual is None or (residual.dtype == torch.float32 and residual.is_contiguous())
     y = torch.empty(B, Hout, Wout, Cout, dtype=torch.float32, device=x2.device)
     part = None
     if gn_stats and (Hout * Wout) % CONV_F16X2_STAT_ROWS == 0:
         part = torch.empty(B * Hout * Wout // CONV_F16X2_STAT_ROWS, Cout // 4, 2, dtype=torch.float32, device=x2.device)
     with _Prof(B * Hout * Wout, Cout, 2 * 3 * Cin3, 1, 1):                # two products per tap over C channels: K_eff = 2 x 9 C
         _lib.check(fn(_lib.ptr(x2), _lib.ptr(w16), y.data_ptr(), B, Hout, Wout, Cin3, Cout, int(upsample),
-                      _lib.ptr(bias), ACT[act], _lib.ptr(residual), zero_page(x2.device).data_ptr(),
-                      float(alpha), _lib.ptr(part), _lib.stream_ptr()))
+                      _lib.ptr(bias), ACT[act], _lib.ptr(residual), zp, float(alpha), _lib.ptr(part), _lib.stream_ptr()))
     if part is not None:
         y.gn_tile_stats = part
     return y
@@ -852,7 +812,6 @@ def image_postprocess(y):
 
 
 # ------------------------------------------------------------------ G-step (training) ops
-ACT_D = {"dgelu_tanh": 5, "dgelu": 6, "mul_aux": 7}   # "mul_aux": y *= aux_in (gated feed-forward)
 
 
 def gemm_train(a, w, bias=None, act=None, alpha=1.0, gate=None, gate_rows=0, residual=None, out=None,
@@ -862,28 +821,21 @@ def gemm_train(a, w, bias=None, act=None, alpha=1.0, gate=None, gate_rows=0, res
     is accumulated into: with splitk == 1 in a fixed order (advgrpo_gemm_bf16_acc_f32, bitwise repeatable), with splitk > 1
     by the split-K atomics (faster for a long contraction, last bits vary from run to run)."""
     lib = _lib.load()
-    K = a.shape[1]
-    M = a.shape[0] if M is None else M
-    N = w.shape[0]
-    if out is not None and out.dtype == torch.float32 and splitk == 1:
+    assert out is not None or splitk == 1
+    acc = out is not None and out.dtype == torch.float32 and splitk == 1      # a running sum, added to in a fixed order
+    M, N, K, out, _, _, code, ld_aux = _linear(a, w, out, out_dtype, None, None, M, act, aux_out, aux_in)
+    if acc:
         assert bias is None and act is None and gate is None and residual is None and aux_out is None and aux_in is None
         with _Prof(M, N, K, 1, 0):
             _lib.check(lib.advgrpo_gemm_bf16_acc_f32(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(),
-                                                     out.stride(0), M, N, K, float(alpha), _lib.stream_ptr()))
+                                                     out.stride(-2), M, N, K, float(alpha), _lib.stream_ptr()))
         return out
-    if out is None:
-        assert splitk == 1
-        out = torch.empty(M, N, dtype=out_dtype, device=a.device)
-    aux = aux_out if aux_out is not None else aux_in
-    code = ACT_D[act] if act in ACT_D else ACT[act]
     with _Prof(M, N, K, splitk, 0):
-      _lib.check(lib.advgrpo_gemm_bf16_train(
-        a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0), _lib.dtype_code(out.dtype),
-        M, N, K, _lib.ptr(bias), code, float(alpha), gate.data_ptr() if gate is not None else None,
-        gate.stride(0) if gate is not None else 0, int(gate_rows), residual.data_ptr() if residual is not None else None,
-        residual.stride(0) if residual is not None else 0, aux_out.data_ptr() if aux_out is not None else None,
-        aux_in.data_ptr() if aux_in is not None else None, aux.stride(0) if aux is not None else 0, int(splitk),
-        _lib.stream_ptr()))
+        _lib.check(lib.advgrpo_gemm_bf16_train(
+            a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(-2), _lib.dtype_code(out.dtype),
+            M, N, K, _lib.ptr(bias), code, float(alpha), _dp(gate), gate.stride(0) if gate is not None else 0, int(gate_rows),
+            _dp(residual), residual.stride(-2) if residual is not None else 0, _dp(aux_out), _dp(aux_in), ld_aux, int(splitk),
+            _lib.stream_ptr()))
     return out
 
 
@@ -962,18 +914,17 @@ def layernorm_mod_bwd(x, dy0, scale0=None, dy1=None, scale1=None, dres=None, row
     M, D = x.shape
     out = torch.empty(M, D, dtype=torch.bfloat16, device=x.device) if out is None else out
     ms = scale0.stride(0) if scale0 is not None else 0
-    dp = lambda t: t.data_ptr() if t is not None else None
     if gates:
         assert 1 <= len(gates) <= 2 and all(g.stride(0) == gates[0].stride(0) and g.stride(1) == 1 for g in gates)
         gouts = [torch.empty(M, D, dtype=torch.bfloat16, device=x.device) for _ in gates]
         _lib.check(lib.advgrpo_layernorm_mod_bwd_gated(
-            x.data_ptr(), x.stride(0), dy0.data_ptr(), dp(dy1), dy0.stride(0), dp(scale0), dp(scale1), ms, int(rows_per_batch), dp(dres),
+            x.data_ptr(), x.stride(0), dy0.data_ptr(), _dp(dy1), dy0.stride(0), _dp(scale0), _dp(scale1), ms, int(rows_per_batch), _dp(dres),
             out.data_ptr(), out.stride(0), M, D, float(eps), gates[0].data_ptr(), gouts[0].data_ptr(),
             gates[1].data_ptr() if len(gates) > 1 else None, gouts[1].data_ptr() if len(gates) > 1 else None, gates[0].stride(0),
             _lib.stream_ptr()))
         return out, gouts
-    _lib.check(lib.advgrpo_layernorm_mod_bwd(x.data_ptr(), x.stride(0), dy0.data_ptr(), dp(dy1), dy0.stride(0), dp(scale0),
-                                             dp(scale1), ms, int(rows_per_batch), dp(dres), out.data_ptr(), out.stride(0),
+    _lib.check(lib.advgrpo_layernorm_mod_bwd(x.data_ptr(), x.stride(0), dy0.data_ptr(), _dp(dy1), dy0.stride(0), _dp(scale0),
+                                             _dp(scale1), ms, int(rows_per_batch), _dp(dres), out.data_ptr(), out.stride(0),
                                              M, D, float(eps), _lib.stream_ptr()))
     return out
 

@@ -148,3 +148,80 @@ def test_gemm_grouped_pair_gate_residual_matches_two_launches():
     oa, ob = ops.gemm_grouped([ops.gemm_desc(xi, wi, bias=bi, gate=gi, gate_rows=Ni, residual=ri),
                                ops.gemm_desc(xt, wt, act="gelu_tanh", gate=gt, gate_rows=Nt, residual=rt)])
     assert torch.equal(oa, a) and torch.equal(ob, b)
+
+
+# ------------------------------------------------------------------------------------- flat entries against the descriptor entry, bit for bit
+# One shape per tile variant a Linear can get (both forms choose alike): 15 ragged in both directions, 2, 1, and the eight-phase kernel (30)
+# at its smallest admissible size.
+FLAT_VS_DESC = [(130, 192, 64, 15), (48, 192, 128, 2), (130, 64, 64, 1), (8192, 1024, 64, 30)]
+
+
+def _flat_vs_desc_operands(M, N, K):
+    g = torch.Generator(device="cuda").manual_seed(M * 7 + N + K)
+    rnd = lambda *s: torch.randn(*s, device="cuda", generator=g)
+    a, w = rnd(M, K).to(torch.bfloat16), (rnd(N, K) * 0.2).to(torch.bfloat16)
+    bias, res = rnd(N).to(torch.bfloat16), rnd(M, N).to(torch.bfloat16)
+    rows = 50
+    gate = rnd((M + rows - 1) // rows, N).to(torch.bfloat16)
+    return a, w, bias, res, gate, rows
+
+
+@pytest.mark.parametrize("M,N,K,variant", FLAT_VS_DESC)
+def test_gemm_equals_its_descriptor_form(M, N, K, variant):
+    """ops.gemm (advgrpo_gemm_bf16) == ops.gemm_grouped of one ops.gemm_desc: bias + gelu_tanh; gate + residual in place; a row scatter of the
+    output with a row gather of the input."""
+    from adv_grpo_amd import _lib, ops
+    assert _lib.load().advgrpo_gemm_variant(M, N, K, 1, 0) == variant
+    a, w, bias, res, gate, rows = _flat_vs_desc_operands(M, N, K)
+    one = lambda **kw: ops.gemm_grouped([ops.gemm_desc(**kw)])[0]
+    assert torch.equal(ops.gemm(a, w, bias=bias, act="gelu_tanh"), one(a=a, w=w, bias=bias, act="gelu_tanh"))
+    assert torch.equal(ops.gemm(a, w, out_dtype=torch.float32, alpha=0.5), one(a=a, w=w, out_dtype=torch.float32, alpha=0.5))
+    r1, r2 = res.clone(), res.clone()
+    assert ops.gemm(a, w, gate=gate, gate_rows=rows, residual=r1, out=r1) is r1
+    one(a=a, w=w, gate=gate, gate_rows=rows, residual=r2, out=r2)
+    assert torch.equal(r1, r2) and not torch.equal(r1, res)
+    # rows [b * sa + 10, b * sa + 10 + h) of a joint input -> rows [b * so + 7, b * so + 7 + h) of a joint output, b = 0, 1
+    h = M // 2
+    sa, so = h + 15, h + 25
+    joint = torch.zeros(2 * sa, K, dtype=torch.bfloat16, device="cuda")
+    joint.view(2, sa, K)[:, 10:10 + h] = a[:2 * h].view(2, h, K)
+    outs = [torch.full((2 * so, N), 3.0, dtype=torch.bfloat16, device="cuda") for _ in range(2)]
+    ops.gemm(joint, w, bias=bias, out=outs[0], seg=(h, so, 7), a_seg=(h, sa, 10), M=2 * h)
+    one(a=joint, w=w, bias=bias, out=outs[1], seg=(h, so, 7), a_seg=(h, sa, 10), M=2 * h)
+    assert torch.equal(outs[0], outs[1])
+    _check(outs[0].view(2, so, N)[:, 7:7 + h].reshape(2 * h, N), _ref(a[:2 * h], w, bias), K)
+    assert (outs[0].view(2, so, N)[:, :7] == 3.0).all() and (outs[0].view(2, so, N)[:, 7 + h:] == 3.0).all()
+
+
+@pytest.mark.parametrize("M,N,K,variant", FLAT_VS_DESC)
+def test_gemm_train_equals_its_descriptor_form(M, N, K, variant):
+    """ops.gemm_train (advgrpo_gemm_bf16_train) == ops.gemm_grouped of one ops.gemm_desc: the epilogues above, the pre-activation copy
+    (aux_out) and the d-activation on aux_in."""
+    from adv_grpo_amd import ops
+    a, w, bias, res, gate, rows = _flat_vs_desc_operands(M, N, K)
+    one = lambda **kw: ops.gemm_grouped([ops.gemm_desc(**kw)])[0]
+    assert torch.equal(ops.gemm_train(a, w, bias=bias, act="gelu_tanh"), one(a=a, w=w, bias=bias, act="gelu_tanh"))
+    r1, r2 = res.clone(), res.clone()
+    ops.gemm_train(a, w, gate=gate, gate_rows=rows, residual=r1, out=r1)
+    one(a=a, w=w, gate=gate, gate_rows=rows, residual=r2, out=r2)
+    assert torch.equal(r1, r2) and not torch.equal(r1, res)
+    pre = [torch.zeros(M, N, dtype=torch.bfloat16, device="cuda") for _ in range(2)]
+    assert torch.equal(ops.gemm_train(a, w, bias=bias, act="gelu_tanh", aux_out=pre[0]), one(a=a, w=w, bias=bias, act="gelu_tanh", aux_out=pre[1]))
+    assert torch.equal(pre[0], pre[1]) and pre[0].any()
+    assert torch.equal(ops.gemm_train(a, w, act="dgelu_tanh", aux_in=pre[0]), one(a=a, w=w, act="dgelu_tanh", aux_in=pre[0]))
+
+
+@pytest.mark.parametrize("out_dtype", [torch.bfloat16, torch.float32])
+def test_bmm_nt_equals_per_batch_gemm(out_dtype):
+    """The batch strides are what only the flat entry sets: operands and output are slices of larger buffers (batch stride != M x pitch)."""
+    from adv_grpo_amd import ops
+    B, M, N, K = 3, 70, 130, 64
+    g = torch.Generator(device="cuda").manual_seed(12)
+    a = torch.randn(B, M + 10, K, device="cuda", generator=g).to(torch.bfloat16)[:, :M]
+    w = torch.randn(B, N + 6, K, device="cuda", generator=g).to(torch.bfloat16)[:, 6:]
+    buf = torch.full((B, M + 2, N), 3.0, dtype=out_dtype, device="cuda")
+    out = ops.bmm_nt(a, w, out=buf[:, :M], alpha=0.25)
+    for b in range(B):
+        assert torch.equal(out[b], ops.gemm(a[b], w[b], alpha=0.25, out_dtype=out_dtype)), b
+    assert (buf[:, M:] == 3.0).all()
+    assert torch.equal(ops.bmm_nt(a, w, out_dtype=out_dtype, alpha=0.25), out)

@@ -335,3 +335,70 @@ def test_backward_and_gate_entries_refuse_bad_arguments_without_launching():
     assert bwd() == 0 and gated() == 0 and gmul() == 0
     torch.cuda.synchronize()
     assert not gout.any() and not t[6].any()
+
+
+# ------------------------------------------------------------------------------------------------- flat LayerNorm entries against the pair entry
+@pytest.mark.parametrize("fp8", [False, True])
+@pytest.mark.parametrize("D", [64, 2056])
+def test_layernorm_mod_flat_entries_equal_the_pair_entry(D, fp8):
+    """ops.layernorm_mod / ops.layernorm_mod_fp8 against ops.layernorm_mod_pair on the same two problems, bit for bit: 5 rows with two
+    outputs and 9 rows with one (a full and a partial four-row block each), both kernel widths, outputs as views of pitch D + 8 / D + 64 in
+    sentinel-filled buffers whose padding must stay untouched."""
+    from adv_grpo_amd import ops
+    g = torch.Generator().manual_seed(D + fp8)
+    probs = []
+    for M, rpb, dual, pad in ((5, 3, True, 8), (9, 4, False, 64)):
+        x = (torch.randn(M, D + 8, generator=g) * 2 + 1).bfloat16().cuda()[:, :D]
+        mods = (torch.randn((M + rpb - 1) // rpb, 4 * D, generator=g) * 0.3).bfloat16().cuda()
+        kw = dict(x=x, scale=mods[:, :D], shift=mods[:, D:2 * D], rows_per_batch=rpb)
+        if dual:
+            kw.update(scale2=mods[:, 2 * D:3 * D], shift2=mods[:, 3 * D:])
+        probs.append((M, pad, dual, kw))
+
+    def run(pair):
+        bufs, kws = [], []
+        for M, pad, dual, kw in probs:
+            kw = dict(kw)
+            b0, kw["out"] = _guard(M, D, pad)
+            b1 = None
+            if dual and (pair or fp8):              # (ops.layernorm_mod allocates its second output itself)
+                b1, kw["out2"] = _guard(M, D, pad)
+            if fp8:
+                for name in ("q", "q2")[:2 if dual else 1]:
+                    codes = torch.full((M + 1, D + 16), 0x5A, dtype=torch.uint8, device="cuda")
+                    scales = torch.full((M + 1,), SENT32, dtype=torch.int32, device="cuda").view(torch.float32)
+                    kw[name] = ops.Fp8Rows(codes[:M, :D], scales[:M])
+                    bufs.append((codes, scales))
+            bufs.append((b0, b1, M))
+            kws.append(kw)
+        if pair:
+            rets = ops.layernorm_mod_pair(*kws)
+        else:
+            rets = []
+            for kw in kws:
+                kw = dict(kw)
+                x = kw.pop("x")
+                rets.append(ops.layernorm_mod_fp8(x, kw.pop("q"), **kw) if fp8 else ops.layernorm_mod(x, **kw))
+        for b in bufs:
+            if len(b) == 3:
+                assert _guard_ok(b[0], b[2], D) and (b[1] is None or _guard_ok(b[1], b[2], D)), (pair, b[2])
+            else:
+                codes, scales = b
+                M = codes.shape[0] - 1
+                assert bool((codes[:, D:] == 0x5A).all()) and bool((codes[M:] == 0x5A).all()) and _is_sent(scales[M:]), (pair, M)
+        return rets, kws
+
+    (fa, fb), fkw = run(False)
+    (pa, pb), pkw = run(True)
+    assert isinstance(fa, tuple) and isinstance(pa, tuple) and len(fa) == len(pa) == 2
+    assert torch.equal(fa[0], pa[0]) and torch.equal(fa[1], pa[1])
+    if fp8:
+        assert fb[1] is None and pb[1] is None and torch.equal(fb[0], pb[0])
+        for f, p in zip(fkw, pkw):
+            for name in ("q", "q2"):
+                if name in f:
+                    assert torch.equal(f[name].q, p[name].q) and torch.equal(f[name].scale, p[name].scale), name
+                    assert f[name].q.any() and not _is_sent(f[name].scale)
+    else:
+        assert torch.is_tensor(fb) and torch.equal(fb, pb)
+    assert not _is_sent(fa[0]) and not _is_sent(fa[1])

@@ -600,3 +600,28 @@ def test_vae_c_entry_refuses_bad_arguments_without_launching():
     assert b"workspace" in lib.advgrpo_last_error()
     assert lib.advgrpo_vae_decode(ctypes.byref(d), lat.data_ptr(), 1, img.data_ptr(), ws.data_ptr() + 16, need, None) != 0      # misaligned
     assert b"workspace" in lib.advgrpo_last_error()
+
+
+def test_conv3x3_x3_both_routes_agree():
+    """The two routes out of advgrpo_conv3x3_nhwc_x3 on one problem: Cout = 128 runs the dedicated split-operand kernel, Cout = 3 (the
+    first three filters of the same weights) the generic implicit-GEMM tile over the tripled contraction axis.  Each is held to the bound
+    test_split_bf16x3_kernels_vs_fp32 uses, 1e-4 of the range of the float64 reference of its own output, so the two differ by at most the
+    sum of the two bounds."""
+    from adv_grpo_amd import ops
+    g = torch.Generator(device="cuda").manual_seed(21)
+    B, H, W, Ci, Co = 1, 8, 8, 64, 128
+    x = torch.randn(B, H, W, Ci, device="cuda", generator=g)
+    wt = torch.randn(Co, Ci, 3, 3, device="cuda", generator=g) / (3 * Ci ** 0.5)
+    bias = torch.randn(Co, device="cuda", generator=g)
+    res = torch.randn(B, H, W, Co, device="cuda", generator=g)
+    w3 = ops.split_x3(wt.permute(0, 2, 3, 1).contiguous(), order=1).reshape(Co, -1)
+    x3 = ops.split_x3(x)
+    wide = ops.conv3x3_x3(x3, w3, bias=bias, residual=res)
+    narrow = ops.conv3x3_x3(x3, w3[:3].contiguous(), bias=bias[:3].contiguous(), residual=res[..., :3].contiguous())
+    ref = torch.nn.functional.conv2d(x.double().permute(0, 3, 1, 2), wt.double(), bias.double(), padding=1).permute(0, 2, 3, 1) + res.double()
+    scale = ref.abs().max().item()
+    assert wide.shape == (B, H, W, Co) and narrow.shape == (B, H, W, 3)
+    assert (wide.double() - ref).abs().max().item() < 1e-4 * scale
+    scale3 = ref[..., :3].abs().max().item()
+    assert (narrow.double() - ref[..., :3]).abs().max().item() < 1e-4 * scale3
+    assert (wide[..., :3] - narrow).abs().max().item() < 1e-4 * (scale + scale3)
