@@ -109,6 +109,12 @@ class Fp8Scales(ctypes.Structure):
     _fields_ = [("a_scale", _P), ("w_scale", _P)]
 
 
+# the leading arguments the text-tower entries share with advgrpo_encode_prompt:
+#   CLIP: ids, tok_emb, pos_emb, vocab, layers (host array), n_layers, final_ln_w, final_ln_b, proj_w
+#   T5:   ids, emb, vocab, rel_table, num_buckets, max_distance, weights (host array of device pointers, 7 per layer), n_layers, final_ln_w
+_CLIP_TOWER = [_P, _P, _P, c_int, POINTER(VitLayer), c_int, _P, _P, _P]
+_T5_TOWER = [_P, _P, c_int, _P, c_int, c_int, POINTER(c_void_p), c_int, _P]
+
 # name -> (restype, argtypes); must list every function include/advgrpo.h declares
 SIGNATURES = {
     "advgrpo_abi_version": (c_int, []),
@@ -174,6 +180,19 @@ SIGNATURES = {
     "advgrpo_vae_encode": (c_int, [POINTER(VaeDecoderDesc), _P, c_int, _P, _P, c_int64, _P]),
     "advgrpo_vit_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "advgrpo_vit_forward": (c_int, [POINTER(VitDesc), _P, c_int64, _P]),
+    # prompt encoding: the row kernels, then the towers (argument order as declared in the header)
+    "advgrpo_token_embed": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "advgrpo_t5_bucket": (c_int, [c_int, c_int, c_int]),
+    "advgrpo_t5_position_bias": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+    "advgrpo_clip_eos_pool": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "advgrpo_prompt_embeds_assemble": (c_int, [_P, c_int, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "advgrpo_clip_text_workspace_bytes": (c_int64, [c_int] * 4),
+    "advgrpo_clip_text_forward": (c_int, _CLIP_TOWER + [c_int] * 7 + [c_float, c_int, _P, _P, c_int64, _P, _P, c_int64, _P]),
+    "advgrpo_t5_workspace_bytes": (c_int64, [c_int] * 5),
+    "advgrpo_t5_forward": (c_int, _T5_TOWER + [c_int] * 6 + [c_float, _P, _P, _P, c_int64, _P]),
+    "advgrpo_encode_prompt_workspace_bytes": (c_int64, [c_int] * 10),
+    "advgrpo_encode_prompt": (c_int, (_CLIP_TOWER + [c_int] * 6) * 2 + [c_float] + _T5_TOWER + [c_int] * 4 + [c_float] +
+                              [c_int, c_int, c_int, _P, _P, _P, _P, c_int64, _P]),
     "advgrpo_gemm_tn_grouped_workspace_bytes": (c_int64, [POINTER(TnDesc), c_int]),
     "advgrpo_gemm_tn_grouped": (c_int, [POINTER(TnDesc), c_int, _P, c_int64, c_int, _P]),
     "advgrpo_lora_merge": (c_int, [_P, c_int, c_int, c_int, c_int, c_float, _P]),

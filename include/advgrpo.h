@@ -644,6 +644,68 @@ typedef struct advgrpo_vit_desc {
 int64_t advgrpo_vit_workspace_bytes(int B, int S, int D, int mlp);
 int advgrpo_vit_forward(const advgrpo_vit_desc* tower, void* workspace /* 256-byte aligned */, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ prompt encoding (SD3: CLIP-L, CLIP-G, T5-XXL v1.1)
+ * encode_prompt (adv_grpo/diffusers_patch/train_dreambooth_lora_sd3.py:98-144, called by compute_text_embeddings,
+ * scripts/train_sd3_fast_pickscore.py:186-193) from token ids; tokenizers are host code outside this library.  First the row kernels that
+ * replace what used to be torch indexing, then the towers.  ids are int64 on the device, every other tensor bf16 unless stated, all
+ * contiguous.  (The Qwen2.5-VL text tower and the Qwen-Image models are not behind entries: still Python launch lists.)
+ *
+ * token_embed: out[b*S + s, :] = bf16(float(tok[ids[b, s]]) + float(pos[s])), bit for bit torch's bf16 `+`; pos may be NULL (T5: a plain
+ * copy of the row).  An id outside [0, vocab) reads nothing from the table and writes a zero row; bad_ids (int32 on the device, may be
+ * NULL) is incremented once per such id.  No device assert, no trap: the caller decides what a bad id means. */
+int advgrpo_token_embed(const int64_t* ids, const void* tok, const void* pos, void* out, int B, int S, int D, int vocab, int* bad_ids,
+                        void* stream);
+/* T5's bidirectional relative-position bucket of rel = key position - query position (transformers T5Attention._relative_position_bucket).
+ * HOST function, no launch; advgrpo_t5_position_bias runs the same routine on the device.  Implemented for (num_buckets, max_distance) =
+ * (32, 128), the T5 / T5 v1.1 encoders' -- there the boundary between two logarithmic buckets is decided in integer arithmetic,
+ * 8 + floor(log2(n * n)) - 6 capped at 15, where a float log may round to either side.  Any other pair: -1 and a message. */
+int advgrpo_t5_bucket(int rel, int num_buckets, int max_distance);
+/* bias[h, i, j] = rel_table[bucket(j - i), h]: rel_table f32 [num_buckets, H] (relative_attention_bias.weight), bias f32 [H, S, S], the
+ * operand of advgrpo_attention_fwd_bias. */
+int advgrpo_t5_position_bias(const float* rel_table, float* bias, int H, int S, int num_buckets, int max_distance, void* stream);
+/* pooled[b, :] = x[b, p_b, :] (x [B, S, D]): CLIPTextTransformer's pooling position.  eos_token_id == 2 (the legacy config.json of the
+ * released CLIP checkpoints): p_b = the FIRST position of the maximum id; otherwise the first position whose id is eos_token_id, or 0
+ * when there is none.  (Padded prompts repeat the eos id to the end of the row.) */
+int advgrpo_clip_eos_pool(const int64_t* ids, const void* x, void* pooled, int B, int S, int D, int eos_token_id, void* stream);
+/* out [B, S + T, Dt]: rows [0, S) = pen_l[b, s, :Dl] | pen_g[b, s, :Dg] | zeros up to Dt, rows [S, S + T) = t5[b, :, :].  One launch writes
+ * every element of out exactly once (no memset in front).  Dl + Dg <= Dt. */
+int advgrpo_prompt_embeds_assemble(const void* pen_l, int Dl, const void* pen_g, int Dg, const void* t5, void* out, int B, int S, int T,
+                                   int Dt, void* stream);
+
+/* The towers.  Like advgrpo_vit_forward: no allocation, no synchronisation, no host <-> device copy (capturable in a graph); the workspace
+ * is the caller's, 256-byte aligned, and the *_workspace_bytes functions are exact upper bounds.  bad_ids as in advgrpo_token_embed.
+ *
+ * CLIP text tower (CLIPTextModelWithProjection; head dim 64): token + position embedding, layers [0, n_layers - 1) through
+ * advgrpo_vit_forward (causal), the penultimate state copied out (hidden_states[-2], [B, S, D]), the last layer, EOS pooling, final
+ * LayerNorm, projection: text_embeds [B, P] with row pitch ld_text_embeds elements.  layers: HOST array of n_layers advgrpo_vit_layer
+ * (ls1 / ls2 NULL); act as advgrpo_gemm_bf16 (4 quick_gelu: CLIP-L, 2 gelu: CLIP-G). */
+int64_t advgrpo_clip_text_workspace_bytes(int B, int S, int D, int mlp);
+int advgrpo_clip_text_forward(const int64_t* ids, const void* tok_emb, const void* pos_emb, int vocab, const advgrpo_vit_layer* layers,
+                              int n_layers, const void* final_ln_w, const void* final_ln_b, const void* proj_w, int B, int S, int D, int H,
+                              int mlp, int P, int act, float eps, int eos_token_id, void* penultimate, void* text_embeds,
+                              int64_t ld_text_embeds, int* bad_ids, void* workspace, int64_t workspace_bytes, void* stream);
+/* T5 v1.1 encoder (T5EncoderModel; d_kv must be 64, inner width H * 64): embedding, the position bias (into the workspace), per block
+ * RMSNorm -> q|k|v GEMM -> attention with the bias (scale 1) -> out-proj + residual -> RMSNorm -> wi_0 with GELU(tanh) -> wi_1 times
+ * that gate -> wo + residual, and the final RMSNorm: out [B, S, D].  weights: HOST array of device pointers, seven per layer in the order
+ *     ln1 [D], qkv [3 H 64, D] (q | k | v rows), o [D, H 64], ln2 [D], wi0 [ff, D], wi1 [ff, D], wo [D, ff]
+ * so layer l's wi0 is weights[7 * l + 4].  rel_table: f32 [num_buckets, H], block 0's relative_attention_bias.weight. */
+int64_t advgrpo_t5_workspace_bytes(int B, int S, int D, int H, int ff);
+int advgrpo_t5_forward(const int64_t* ids, const void* emb, int vocab, const float* rel_table, int num_buckets, int max_distance,
+                       const void* const* weights, int n_layers, const void* final_ln_w, int B, int S, int D, int H, int d_kv, int ff,
+                       float eps, void* out, int* bad_ids, void* workspace, int64_t workspace_bytes, void* stream);
+/* encode_prompt: CLIP-L (l_*), CLIP-G (g_*) over S tokens, T5 (t_*) over T tokens, arguments as the two entries above ->
+ * prompt_embeds [B, S + T, Dt] (advgrpo_prompt_embeds_assemble) and pooled [B, Pl + Pg] (the two text_embeds side by side; Pl % 8 == 0).
+ * Every refusal comes before the first launch. */
+int64_t advgrpo_encode_prompt_workspace_bytes(int B, int S, int T, int Dl, int mlp_l, int Dg, int mlp_g, int Dt, int Ht, int ff);
+int advgrpo_encode_prompt(
+    const int64_t* ids_l, const void* l_tok, const void* l_pos, int l_vocab, const advgrpo_vit_layer* l_layers, int l_n_layers,
+    const void* l_ln_w, const void* l_ln_b, const void* l_proj, int Dl, int Hl, int mlp_l, int Pl, int act_l, int eos_l,
+    const int64_t* ids_g, const void* g_tok, const void* g_pos, int g_vocab, const advgrpo_vit_layer* g_layers, int g_n_layers,
+    const void* g_ln_w, const void* g_ln_b, const void* g_proj, int Dg, int Hg, int mlp_g, int Pg, int act_g, int eos_g, float clip_eps,
+    const int64_t* ids_t5, const void* t_emb, int t_vocab, const float* rel_table, int num_buckets, int max_distance,
+    const void* const* t_weights, int t_n_layers, const void* t_final_ln_w, int Dt, int Ht, int d_kv, int ff, float t5_eps,
+    int B, int S, int T, void* prompt_embeds, void* pooled, int* bad_ids, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ fp8 Linears (BASELINE config 5: "fp8 MFMA path")
  * The reference has no fp8 code (config 5 changes pretrained.model / resolution only); the scheme is this
  * library's: OCP e4m3 codes, one f32 scale per token row of the activation and per output channel of the weight,

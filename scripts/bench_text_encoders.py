@@ -32,10 +32,42 @@ def t5_sd(D=4096, H=64, ff=10240, L=24, vocab=32128):
 cl = te.CLIPTextEncoder(clip_sd(768, 3072, 12, 768), 12, 12, "quick_gelu", 2, dev)
 cg = te.CLIPTextEncoder(clip_sd(1280, 5120, 32, 1280), 32, 20, "gelu", 2, dev)
 t5 = te.T5Encoder(t5_sd(), 24, 64, device=dev)
-for B in (1, 16):
+
+
+def timed(fn, runs):
+    """Host-inclusive milliseconds of each of `runs` calls (host clock around work that ends in a device synchronise)."""
+    out = []
+    for _ in range(runs):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize(); out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+def bias_fresh(method):
+    t5._bias.clear(); t5._bias_torch.clear()       # position_bias caches per S: time the making, not the lookup
+    return method(128)
+
+
+import json, statistics
+RUNS, ROUNDS = 7, 3
+result = {"bench": "text_encoders", "shapes": "CLIP-L 12x768, CLIP-G 32x1280, T5 24x4096, S=77, T=128", "runs_per_median": RUNS, "rounds": ROUNDS}
+for B in (1, 8):
     ids = torch.randint(3, 30000, (B, 77), device=dev); ids_t5 = torch.randint(3, 30000, (B, 128), device=dev)
-    for _ in range(2): pe, pooled = te.encode_prompt(cl, cg, t5, ids, ids, ids_t5)
-    torch.cuda.synchronize(); t0 = time.time()
-    for _ in range(5): pe, pooled = te.encode_prompt(cl, cg, t5, ids, ids, ids_t5)
-    torch.cuda.synchronize(); dt = (time.time() - t0) / 5
-    print(f"encode_prompt B={B}: {dt * 1e3:.2f} ms  -> {tuple(pe.shape)} {tuple(pooled.shape)} finite={bool(torch.isfinite(pe.float()).all())}")
+    entry = lambda: te.encode_prompt(cl, cg, t5, ids, ids, ids_t5)
+    seq = lambda: te.encode_prompt(cl, cg, t5, ids, ids, ids_t5, sequenced=True)     # the launches one by one: the parent commit's encode_prompt
+    for _ in range(2):
+        a, b = entry(), seq()
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and bool(torch.isfinite(a[0].float()).all())
+    med = {"entry": [], "sequenced": []}
+    for _ in range(ROUNDS):                         # the two paths alternate in one process; the spread is that of the repeated medians
+        med["entry"].append(statistics.median(timed(entry, RUNS)))
+        med["sequenced"].append(statistics.median(timed(seq, RUNS)))
+    for k, v in med.items():
+        result[f"encode_prompt_{k}_ms_B{B}"] = round(statistics.median(v), 3)
+        result[f"encode_prompt_{k}_spread_ms_B{B}"] = round(max(v) - min(v), 3)
+bias_fresh(t5.position_bias); bias_fresh(t5.position_bias_torch)
+for name, method in (("kernel", t5.position_bias), ("torch", t5.position_bias_torch)):
+    result[f"position_bias_128_{name}_ms"] = round(statistics.median(timed(lambda: bias_fresh(method), 3 * RUNS)), 4)
+result["bad_ids"] = te.bad_id_count()
+print(json.dumps(result))
