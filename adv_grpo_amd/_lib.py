@@ -193,6 +193,13 @@ SIGNATURES = {
     "advgrpo_encode_prompt_workspace_bytes": (c_int64, [c_int] * 10),
     "advgrpo_encode_prompt": (c_int, (_CLIP_TOWER + [c_int] * 6) * 2 + [c_float] + _T5_TOWER + [c_int] * 4 + [c_float] +
                               [c_int, c_int, c_int, _P, _P, _P, _P, c_int64, _P]),
+    # the Qwen2.5-VL prompt encoder: fused grouped-query attention, the head plumbing of the materialised path, the tower
+    "advgrpo_attention_fwd_gqa": (c_int, [_P, _P, _P, _P] + [c_int64] * 8 + [c_int] * 5 + [c_float, c_int, _P]),
+    "advgrpo_gqa_pack_heads": (c_int, [_P, c_int64, _P, _P, _P] + [c_int] * 5 + [_P]),
+    "advgrpo_gqa_unpack_heads": (c_int, [_P, _P] + [c_int] * 4 + [_P]),
+    "advgrpo_qwen_prompt_embeds": (c_int, [_P, _P, _P, _P] + [c_int] * 5 + [_P, _P]),
+    "advgrpo_qwen_text_workspace_bytes": (c_int64, [c_int] * 8),
+    "advgrpo_qwen_text_forward": (c_int, [_P, _P, c_int, POINTER(c_void_p), c_int, _P, _P] + [c_int] * 7 + [c_float, c_int, _P, _P, _P, c_int64, _P]),
     "advgrpo_gemm_tn_grouped_workspace_bytes": (c_int64, [POINTER(TnDesc), c_int]),
     "advgrpo_gemm_tn_grouped": (c_int, [POINTER(TnDesc), c_int, _P, c_int64, c_int, _P]),
     "advgrpo_lora_merge": (c_int, [_P, c_int, c_int, c_int, c_int, c_float, _P]),

@@ -10,18 +10,31 @@ It runs once per prompt (as the SD3 towers do: 3.6 % of a rollout step there), s
 new ones: RMSNorm rows, fused q|k|v Linear, `advgrpo_rope_half` (rotate_half rotary on the 28 query + 4 key heads in place), causal
 grouped-query attention over MATERIALISED scores (prompts are <= 512 tokens: batched GEMMs on head-major copies +
 `advgrpo_softmax_rows_causal`; right padding needs no extra mask -- a valid query only sees keys before it), SiLU-gated feed-forward
-through the `silu` and `mul_aux` GEMM epilogues."""
+through the `silu` and `mul_aux` GEMM epilogues.
+
+By default the whole tower is ONE call of `advgrpo_qwen_text_forward` (csrc/qwen_text_encoder.cpp: the same kernels in the same order, the
+torch indexing of the attention step as the `advgrpo_gqa_pack_heads` / `advgrpo_gqa_unpack_heads` kernels; bit-identical), and the launch
+list below stays as the check (`sequenced=True`).  `attention="fused"` is the opt-in that replaces the materialised scores by
+`advgrpo_attention_fwd_gqa` on the q|k|v buffer in place: no head-major copies, and prompts beyond 512 tokens."""
+import ctypes
+
 import torch
 
 from . import _lib, ops
+from .text_encoders import _bad_ids, _workspace
 from .vit import _bf
 
 DROP_IDX = 34      # QwenImagePipeline.prompt_template_encode_start_idx
+ATTENTION_MODES = {"materialised": 0, "fused": 1}      # advgrpo_qwen_text_forward's attention_mode
 
 
 class Qwen25VLTextEncoder:
-    def __init__(self, sd, cfg, device="cuda"):
-        self.cfg, self.device = cfg, torch.device(device)
+    _ORDER = ("ln1", "qkv.w", "qkv.b", "o", "ln2", "gate", "up", "down")     # a layer's eight pointers in advgrpo_qwen_text_forward's `weights`
+
+    def __init__(self, sd, cfg, device="cuda", attention="materialised"):
+        if attention not in ATTENTION_MODES:
+            raise ValueError(f"Qwen25VLTextEncoder: attention must be one of {sorted(ATTENTION_MODES)} (got {attention!r})")
+        self.cfg, self.device, self.attention = cfg, torch.device(device), attention
         dev = self.device
         self.embed = _bf(sd["embed_tokens.weight"], dev)
         self.final_w = _bf(sd["norm.weight"], dev)
@@ -34,7 +47,14 @@ class Qwen25VLTextEncoder:
                 "qkv.b": _bf(torch.cat([sd[f"{a}.q_proj.bias"], sd[f"{a}.k_proj.bias"], sd[f"{a}.v_proj.bias"]]), dev),
                 "o": _bf(sd[f"{a}.o_proj.weight"], dev), "gate": _bf(sd[f"{p}.mlp.gate_proj.weight"], dev),
                 "up": _bf(sd[f"{p}.mlp.up_proj.weight"], dev), "down": _bf(sd[f"{p}.mlp.down_proj.weight"], dev)})
-        self._cs = {}
+        self._cs, self._tower = {}, None
+
+    def tower_args(self):
+        """The arguments of advgrpo_qwen_text_forward between `ids` and `cos_sin`, built once."""
+        if self._tower is None:
+            tab = (ctypes.c_void_p * (8 * len(self.layers)))(*[L[n].data_ptr() for L in self.layers for n in self._ORDER])
+            self._tower = (self.embed.data_ptr(), self.embed.shape[0], tab, len(self.layers), self.final_w.data_ptr())
+        return self._tower
 
     def _cos_sin(self, T):
         def make():
@@ -64,14 +84,28 @@ class Qwen25VLTextEncoder:
         return o[:, :T].reshape(B, H, T, hd).permute(0, 2, 1, 3).reshape(B * T, H * hd).contiguous()
 
     @torch.no_grad()
-    def __call__(self, input_ids, attention_mask=None):
+    def __call__(self, input_ids, attention_mask=None, sequenced=False):
         """-> hidden_states[-1] [B, T, hidden] bf16.  (Right padding needs no mask: see the module docstring; the rows of padding
-        tokens are computed and meaningless, as in transformers.)"""
+        tokens are computed and meaningless, as in transformers.)  One call of advgrpo_qwen_text_forward; sequenced=True: the
+        materialised path launch by launch (the check).  An id outside the vocabulary embeds as a zero row and is counted
+        (text_encoders.bad_id_count)."""
         cfg, lib = self.cfg, _lib.load()
         B, T = input_ids.shape
-        if T > 512:
-            raise ValueError(f"Qwen25VLTextEncoder: prompts of up to 512 tokens (got {T})")
+        if T > 512 and (sequenced or self.attention == "materialised"):
+            raise ValueError(f"Qwen25VLTextEncoder: the materialised attention holds prompts of up to 512 tokens (got {T}); "
+                             'build the encoder with attention="fused" for longer ones')
         H, KV, hd, D = cfg.num_heads, cfg.num_kv_heads, cfg.head_dim, cfg.hidden_size
+        if not sequenced:
+            dev, mode = self.device, ATTENTION_MODES[self.attention]
+            ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
+            cs = self._cos_sin(T)
+            nbytes = int(lib.advgrpo_qwen_text_workspace_bytes(B, T, D, H, KV, hd, cfg.intermediate_size, mode))
+            out = torch.empty(B, T, D, dtype=torch.bfloat16, device=dev)
+            ws = _workspace(nbytes, dev)
+            _lib.check(lib.advgrpo_qwen_text_forward(ids.data_ptr(), *self.tower_args(), cs.data_ptr(), B, T, D, H, KV, hd, cfg.intermediate_size,
+                                                     float(cfg.rms_eps), mode, out.data_ptr(), _bad_ids(dev).data_ptr(), ws.data_ptr(), nbytes,
+                                                     _lib.stream_ptr()))
+            return out
         x = self.embed[input_ids.to(self.device)].reshape(B * T, D).contiguous()
         cs = self._cos_sin(T)
         for L in self.layers:
@@ -87,13 +121,23 @@ class Qwen25VLTextEncoder:
         return ops.rmsnorm_rows(x, self.final_w, eps=cfg.rms_eps).view(B, T, D)
 
     @torch.no_grad()
-    def encode_prompt(self, input_ids, attention_mask, drop_idx=DROP_IDX):
+    def encode_prompt(self, input_ids, attention_mask, drop_idx=DROP_IDX, sequenced=False):
         """_get_qwen_prompt_embeds after tokenisation: (prompt_embeds [B, Lmax, hidden] bf16, mask [B, Lmax]) -- each sample's valid tokens
         minus the first drop_idx template tokens, right-padded with zeros.  The lengths come from the HOST copy of the mask (the
-        tokenizer's output): no device synchronisation."""
-        hs = self(input_ids, attention_mask)
+        tokenizer's output): no device synchronisation; they reach advgrpo_qwen_prompt_embeds through one small host-to-device copy.
+        sequenced=True: the launch-by-launch tower and the assembly by a Python loop over the samples (the check)."""
+        hs = self(input_ids, attention_mask, sequenced=sequenced)
         lens = [int(n) for n in attention_mask.cpu().sum(dim=1)]
         L = max(n - drop_idx for n in lens)
+        if not sequenced and L > 0:
+            B, T, D = hs.shape
+            host = torch.tensor(lens, dtype=torch.int32)
+            dlens = (host.pin_memory() if hs.is_cuda else host).to(hs.device, non_blocking=True)
+            emb = torch.empty(B, L, D, dtype=hs.dtype, device=hs.device)
+            msk = torch.empty(B, L, dtype=torch.long, device=hs.device)
+            _lib.check(_lib.load().advgrpo_qwen_prompt_embeds(hs.data_ptr(), dlens.data_ptr(), emb.data_ptr(), msk.data_ptr(), B, T, D, L,
+                                                              int(drop_idx), _bad_ids(hs.device).data_ptr(), _lib.stream_ptr()))
+            return emb, msk
         emb = torch.zeros(hs.shape[0], L, hs.shape[2], dtype=hs.dtype, device=hs.device)
         msk = torch.zeros(hs.shape[0], L, dtype=torch.long, device=hs.device)
         for b, n in enumerate(lens):

@@ -648,7 +648,7 @@ int advgrpo_vit_forward(const advgrpo_vit_desc* tower, void* workspace /* 256-by
  * encode_prompt (adv_grpo/diffusers_patch/train_dreambooth_lora_sd3.py:98-144, called by compute_text_embeddings,
  * scripts/train_sd3_fast_pickscore.py:186-193) from token ids; tokenizers are host code outside this library.  First the row kernels that
  * replace what used to be torch indexing, then the towers.  ids are int64 on the device, every other tensor bf16 unless stated, all
- * contiguous.  (The Qwen2.5-VL text tower and the Qwen-Image models are not behind entries: still Python launch lists.)
+ * contiguous.  (The Qwen2.5-VL text tower has its own section below; the Qwen-Image MMDiT and VAE are still Python launch lists.)
  *
  * token_embed: out[b*S + s, :] = bf16(float(tok[ids[b, s]]) + float(pos[s])), bit for bit torch's bf16 `+`; pos may be NULL (T5: a plain
  * copy of the row).  An id outside [0, vocab) reads nothing from the table and writes a zero row; bad_ids (int32 on the device, may be
@@ -705,6 +705,51 @@ int advgrpo_encode_prompt(
     const int64_t* ids_t5, const void* t_emb, int t_vocab, const float* rel_table, int num_buckets, int max_distance,
     const void* const* t_weights, int t_n_layers, const void* t_final_ln_w, int Dt, int Ht, int d_kv, int ff, float t5_eps,
     int B, int S, int T, void* prompt_embeds, void* pooled, int* bad_ids, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ prompt encoding (Qwen-Image: the Qwen2.5-VL language model)
+ * What QwenImagePipeline._get_qwen_prompt_embeds computes after tokenisation (BASELINE config 5; the reference names the config at
+ * config/grpo.py:324,330 and ships no code for it).  ids int64 on the device, every other tensor bf16 unless stated, all contiguous.
+ *
+ * attention_fwd_gqa: o = softmax(q k^T * scale [+ causal mask]) v for SELF-attention with Hq query heads over Hkv key/value heads, query
+ * head h reading key/value head h / (Hq / Hkv); bf16 in/out, f32 scores / exponentials / row maximum / row sum, probabilities rounded to
+ * bf16 before P V, the quotient rounded to bf16.  Views as for advgrpo_attention_fwd: element (b, s, h, d) at ptr + b*bs + s*ld +
+ * h*head_dim + d, so the three pointers may look into one [B S, (Hq + 2 Hkv) 128] GEMM output.  head_dim 128 only; Hq % Hkv == 0 (Hkv == Hq
+ * is plain multi-head attention); ld{q,k,v,o} % 8 == 0, bs* % 8 == 0, 16-byte aligned pointers.  A workgroup stages each K / V tile once
+ * for up to 8 query heads of a group.  Online softmax with a running maximum: no fallback path, the fallback counters are not touched.
+ * All offsets are 64-bit.  No lse, no bias, no backward. */
+int advgrpo_attention_fwd_gqa(const void* q, const void* k, const void* v, void* o,
+                              int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                              int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso,
+                              int B, int Hq, int Hkv, int S, int head_dim, float scale, int causal, void* stream);
+/* gqa_pack_heads: packed rows qkv [B T, ld] (q | k | v: H + KV + KV heads of head_dim, ld % 8 == 0) -> the operands of the materialised
+ * attention: q [B H, Tp, head_dim], k [B H, Tp, head_dim] (key/value head h / (H / KV) written for query head h), vt [B H, head_dim, Tp];
+ * Tp = ceil(T / 64) 64 and the padding positions are written as zeros by the kernel (no memset in front).  head_dim % 8 == 0.
+ * gqa_unpack_heads: o [B H, Tp, head_dim] -> out [B T, H head_dim]. */
+int advgrpo_gqa_pack_heads(const void* qkv, int64_t ld, void* q, void* k, void* vt, int B, int T, int H, int KV, int head_dim, void* stream);
+int advgrpo_gqa_unpack_heads(const void* o, void* out, int B, int T, int H, int head_dim, void* stream);
+/* qwen_prompt_embeds: hidden [B, T, D] and lens (int32 [B] on the device: valid tokens per sample, template included) -> emb [B, L, D]
+ * with rows drop_idx .. lens[b] - 1 of sample b at rows 0 .. lens[b] - drop_idx - 1 and zeros behind them, mask [B, L] int64 (1 on those
+ * rows).  Every element of both is written.  A length outside [drop_idx, T] is clamped into it and counted once in bad (int32 on the
+ * device, may be NULL).  No device assert. */
+int advgrpo_qwen_prompt_embeds(const void* hidden, const int* lens, void* emb, int64_t* mask, int B, int T, int D, int L, int drop_idx, int* bad,
+                               void* stream);
+/* The tower: token embedding (advgrpo_token_embed: an id outside the vocabulary embeds as a zero row and is counted in bad_ids), per
+ * layer RMSNorm -> q|k|v GEMM with bias -> advgrpo_rope_half on the H + KV query and key heads -> causal grouped-query attention ->
+ * out-proj + residual -> RMSNorm -> gate with SiLU -> up times that gate -> down + residual, and the final RMSNorm: out [B, T, D],
+ * hidden_states[-1].  weights: HOST array of device pointers, EIGHT per layer in the order
+ *     ln1 [D], qkv.w [(H + 2 KV) head_dim, D] (q | k | v rows), qkv.b [(H + 2 KV) head_dim], o [D, H head_dim], ln2 [D],
+ *     gate [ff, D], up [ff, D], down [D, ff]
+ * so layer l's gate is weights[8 * l + 5].  cos_sin: f32 [T, head_dim / 2, 2] on the device (rotary table, as for advgrpo_rope_half).
+ * attention_mode 0 (materialised): pack -> batched score GEMM (f32, into the workspace) -> advgrpo_softmax_rows_causal -> batched P V GEMM
+ *   -> unpack; bit-identical to the Python launch list; T <= 512; head_dim % 64 == 0.
+ * attention_mode 1 (fused): advgrpo_attention_fwd_gqa on the q|k|v buffer in place; head_dim == 128; no cap on T of its own.
+ * Both modes: B * T <= 2^20 rows, D % 64 == 0, D <= 4096, ff % 64 == 0; no allocation, no synchronisation, no host <-> device copy.  The
+ * workspace (256-byte aligned) is carved in the order the size function adds it up; the size function returns 0 for a shape or mode the
+ * entry refuses outright.  Every refusal comes before the first launch. */
+int64_t advgrpo_qwen_text_workspace_bytes(int B, int T, int D, int H, int KV, int head_dim, int ff, int attention_mode);
+int advgrpo_qwen_text_forward(const int64_t* ids, const void* emb, int vocab, const void* const* weights, int n_layers, const void* final_w,
+                              const float* cos_sin, int B, int T, int D, int H, int KV, int head_dim, int ff, float eps, int attention_mode,
+                              void* out, int* bad_ids, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ fp8 Linears (BASELINE config 5: "fp8 MFMA path")
  * The reference has no fp8 code (config 5 changes pretrained.model / resolution only); the scheme is this
