@@ -328,6 +328,14 @@ static int gemm_prepare(GemmParams& p) {
                   "gemm: accumulation into C is a plain f32 GEMM without other epilogue");
     ADVGRPO_CHECK(p.act < ACT_DGELU_TANH || p.aux_in, "gemm: d-activation epilogue needs aux_in");
     ADVGRPO_CHECK(!(p.aux_out || p.aux_in) || ((p.ld_aux & 3) == 0 && (p.N & 3) == 0), "gemm: aux needs N, ld_aux %% 4 == 0");
+    // aux_out and the d-activations exist in the 4-column forms of the epilogue only: the scalar branch of gemm_epilogue_frag (taken when
+    // ldc, ldr or gate_stride is no multiple of 4) neither stores aux_out nor reads aux_in
+    if (p.aux_out || p.aux_in || p.act >= ACT_DGELU_TANH) {
+        ADVGRPO_CHECK((p.ldc & 3) == 0, "gemm: aux / d-activation needs ldc %% 4 == 0 (ldc=%lld)", (long long)p.ldc);
+        ADVGRPO_CHECK((p.ldr & 3) == 0, "gemm: aux / d-activation needs ldr %% 4 == 0 (ldr=%lld)", (long long)p.ldr);
+        ADVGRPO_CHECK((p.gate_stride & 3) == 0, "gemm: aux / d-activation needs gate_stride %% 4 == 0 (gate_stride=%lld)",
+                      (long long)p.gate_stride);
+    }
     int variant = gemm_variant(p.M, p.N, p.K, p.batch * p.splitk, p.conv, p.splitk == 1 && !p.conv);
 #ifdef ADVGRPO_EXPERIMENTS   // ADVGRPO_GEMM_FORCE_NK=N:K:variant overrides the tile variant of one Linear shape
     if (knobs().fn == p.N && knobs().fk == p.K && !p.conv && p.splitk == 1 && p.M >= 8192) variant = knobs().fv;

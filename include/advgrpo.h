@@ -489,7 +489,9 @@ int advgrpo_pickscore_pairs(const void* image_embs, const void* text_embs, int B
  *     called from the transformer at adv_grpo/diffusers_patch/sd3_pipeline_with_logprob_fast.py:168-186):
  *     y = bf16(bf16(x) * rsqrt(mean(x^2) + eps)) * w[head / heads_per_weight]; rms_rs_out[orow, head] keeps 1/rms;
  *   - a grouped launch: descs[0] and descs[1] (count = 2) are served by ONE kernel launch, the second problem's
- *     tiles filling the tail of the first (the text-stream Linear of a joint block next to its image-stream twin). */
+ *     tiles filling the tail of the first (the text-stream Linear of a joint block next to its image-stream twin).
+ * aux_out, aux_in and the d-activations (act 5 / 6 / 7) need N, ld_aux, ldc, ldr and gate_stride to be multiples of 4: every other
+ * pitch is refused before the launch with a message that names it (the epilogue's scalar form carries no aux). */
 typedef struct advgrpo_gemm_desc {
     const void* A; const void* W; void* C;
     int64_t lda, ldw, ldc;

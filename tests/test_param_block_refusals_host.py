@@ -45,6 +45,15 @@ TXT_SPLITK = "gemm: split-K accumulates atomically into f32 and takes no other e
 TXT_ACC = "gemm: accumulation into C is a plain f32 GEMM without other epilogue"
 TXT_DACT = "gemm: d-activation epilogue needs aux_in"
 TXT_AUX = "gemm: aux needs N, ld_aux % 4 == 0"
+TXT_AUX_LDC = "gemm: aux / d-activation needs ldc % 4 == 0 (ldc=130)"
+TXT_AUX_LDR = "gemm: aux / d-activation needs ldr % 4 == 0 (ldr=134)"
+TXT_AUX_GATE = "gemm: aux / d-activation needs gate_stride % 4 == 0 (gate_stride=138)"
+# aux_out / a d-activation on a pitch that would take the scalar form of the epilogue, which carries neither
+AUX_PITCH = [(dict(aux_out=P, ld_aux=128, ldc=130), TXT_AUX_LDC), (dict(aux_in=P, ld_aux=128, act=5, ldc=130), TXT_AUX_LDC),
+             (dict(aux_in=P, ld_aux=128, act=7, residual=P, ldr=134), TXT_AUX_LDR), (dict(aux_out=P, ld_aux=128, act=1, ldr=134), TXT_AUX_LDR),
+             (dict(aux_in=P, ld_aux=128, act=6, gate=P, gate_stride=138, gate_rows=16), TXT_AUX_GATE),
+             (dict(aux_out=P, ld_aux=128, ldc=130, ldr=134, gate_stride=138), TXT_AUX_LDC),          # the order of the three checks
+             (dict(aux_out=P, ld_aux=126, ldc=130), TXT_AUX)]                                        # after the N / ld_aux check
 TXT_RMS = "gemm: fused QK-norm needs a plain bf16 projection with N % 64 == 0 and 16-byte aligned rows"
 COMMON = [(dict(A=None), TXT_NULL), (dict(W=None), TXT_NULL), (dict(C=None), TXT_NULL), (dict(K=96), TXT_K), (dict(lda=60), TXT_LD),
           (dict(ldw=60), TXT_LD)]
@@ -93,7 +102,7 @@ def test_gemm_bf16_refusals(lib, over, text):
     (dict(aux_out=P, ld_aux=126), TXT_AUX), (dict(aux_in=P, ld_aux=128, act=5, N=126), TXT_AUX),
     (dict(rms_weight=P, rms_nheads=2, rms_heads_per_weight=1, gate=P, gate_stride=128, gate_rows=16), TXT_RMS),
     (dict(rms_weight=P, rms_nheads=2, rms_heads_per_weight=1, out_dtype=F32), TXT_RMS),
-    (dict(rms_weight=P, rms_nheads=0, rms_heads_per_weight=1), TXT_RMS)])
+    (dict(rms_weight=P, rms_nheads=0, rms_heads_per_weight=1), TXT_RMS)] + AUX_PITCH)
 def test_gemm_grouped_refusals(lib, over, text):
     _refused(lib, _grouped(lib, _desc(**over)), text)
     _refused(lib, _grouped(lib, _desc(**over), _desc()), text)          # as the first of a pair
@@ -122,7 +131,7 @@ def test_gemm_fp8_grouped_refusals(lib):
 @pytest.mark.parametrize("over,text", COMMON + [
     (dict(out_dtype=2), TXT_DT), (dict(splitk=2, out_dtype=F32, bias=P), TXT_SPLITK), (dict(splitk=2), TXT_SPLITK),
     (dict(splitk=2, out_dtype=F32, aux_out=P, ld_aux=128), TXT_SPLITK), (dict(act=5), TXT_DACT), (dict(act=6), TXT_DACT),
-    (dict(aux_out=P, ld_aux=128, N=126), TXT_AUX), (dict(aux_in=P, ld_aux=130, act=5), TXT_AUX)])
+    (dict(aux_out=P, ld_aux=128, N=126), TXT_AUX), (dict(aux_in=P, ld_aux=130, act=5), TXT_AUX)] + AUX_PITCH)
 def test_gemm_bf16_train_refusals(lib, over, text):
     _refused(lib, _train(lib, **over), text)
 
