@@ -10,7 +10,7 @@ from ctypes import c_double, c_float, c_int, c_int32, c_int64, c_uint64, c_void_
 
 import torch
 
-F32, BF16, F64, U8 = 0, 1, 2, 3
+F32, BF16, F64, U8, I32, I64 = 0, 1, 2, 3, 4, 5
 JPEG_NCHW, JPEG_NHWC = 0, 1
 SDE_EPS, SDE_PHILOX, SDE_REPLAY = 0, 1, 2
 
@@ -270,6 +270,10 @@ SIGNATURES = {
     "advgrpo_attention_fwd": (c_int, [_P, _P, _P, _P] + [c_int64] * 8 + [c_int] * 5 + [c_float, c_int, _P, _P]),
     "advgrpo_attention_fallback_count": (c_int, [POINTER(ctypes.c_longlong), c_int]),
     "advgrpo_attention_bwd": (c_int, [_P] * 10 + [c_int64] * 12 + [c_int] * 5 + [c_float, _P]),
+    # per-sample lengths (head dim 128): S in place of Sq / Skv, seq_lens int32 [B] on the device
+    "advgrpo_attention_fwd_varlen": (c_int, [_P, _P, _P, _P] + [c_int64] * 8 + [c_int] * 4 + [c_float, _P, _P, _P]),
+    "advgrpo_attention_bwd_varlen": (c_int, [_P] * 10 + [c_int64] * 12 + [c_int] * 4 + [c_float, _P, _P]),
+    "advgrpo_mask_to_seq_lens": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, _P]),
     "advgrpo_jpeg_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "advgrpo_jpeg_max_file_bytes": (c_int64, [c_int, c_int]),
     "advgrpo_jpeg_encode": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, c_int64, _P]),

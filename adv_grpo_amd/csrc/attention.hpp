@@ -17,6 +17,11 @@ struct AttnParams {
     int nqb, nwg, xcd_local;      // query blocks per (b,h); workgroups in the 1-D grid; XCD-local block order (common.hpp)
 };
 
+// the head-dim-128 kernel with per-sample lengths: the same block + the lengths (int32 [B] on the device)
+struct AttnVarlenParams : AttnParams {
+    const int* seq_lens;
+};
+
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 constexpr int ATT_QB = 128;   // queries per workgroup
@@ -46,6 +51,9 @@ __device__ __forceinline__ void att_dma16(const void* src, const char* lds) {
 int attention_fwd_pipe_launch(const AttnParams& p, hipStream_t s);
 // head dim 128 (attention_d128.hip): 8-wave workgroups of 256 queries, non-causal, no score bias, 16-byte aligned output rows
 int attention_fwd_d128_launch(const AttnParams& p, int B, hipStream_t s);
+// the same with per-sample lengths read from a device array (self-attention, p.Sq == p.Skv = the padded length): sample b is computed as
+// if launched alone at seq_lens[b] (clamped into [1, S]); the rows beyond it are written as zeros
+int attention_fwd_d128_varlen_launch(const AttnParams& p, int B, const int* seq_lens, hipStream_t s);
 // workgroups of the two kernels above that took their running-maximum fallback since the last reset (host call, synchronises)
 int attention_pipe_fallbacks(unsigned long long* out, int reset);
 int attention_d128_fallbacks(unsigned long long* out, int reset);

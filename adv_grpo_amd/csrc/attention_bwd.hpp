@@ -19,9 +19,16 @@ struct AttnBwdParams {
     int xcd_local;                // XCD-local block order (common.hpp xcd_local_bh)
 };
 
+struct AttnBwdVarlenParams : AttnBwdParams {
+    const int* seq_lens;          // int32 [B] on the device (attention_bwd_d128.hip, the VARLEN instantiations)
+};
+
 // dQ (DKDV = false) and dK / dV (true): software-pipelined kernels of attention_bwd_pipe.hip
 int attention_bwd_pipe_launch(const AttnBwdParams& p, int B, hipStream_t s);
 // head dim 128 (attention_bwd_d128.hip): its own delta kernel writes D[b,h,q] = sum_d O dO as a plain [B,H,Sq] array into p.vec
 int attention_bwd_d128_launch(const AttnBwdParams& p, int B, hipStream_t s);
+// the same with per-sample lengths from a device array (self-attention, p.Sq == p.Skv = the padded length; lse and p.vec keep the padded
+// pitch): sample b as if launched alone at seq_lens[b] (clamped into [1, S]); dq / dk / dv rows beyond it are written as zeros
+int attention_bwd_d128_varlen_launch(const AttnBwdParams& p, int B, const int* seq_lens, hipStream_t s);
 
 }  // namespace advgrpo

@@ -40,8 +40,26 @@ typedef __bf16 bf16x2v_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack2(f32x2_t v) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2v_t)); }   // v_cvt_pk_bf16_f32
 __device__ __forceinline__ uint32_t b8_pack(float lo, float hi) { return pack2(f32x2_t{lo, hi}); }
 
-template <bool DKDV, int B8_CB>
-__global__ __launch_bounds__(256, B8_CB == 1 ? (DKDV ? 3 : 4) : 2) void attn_bwd_d128_kernel(const AttnBwdParams p) {
+// per-sample length of the VARLEN bodies: seq_lens[b] clamped into [1, S], wave-uniform
+__device__ __forceinline__ int b8_len(const int* __restrict__ seq_lens, int b, int S) {
+    return __builtin_amdgcn_readfirstlane(min(max(seq_lens[b], 1), S));
+}
+// zero rows r0 .. r0 + nrows - 1 (below S) of one head's 128 columns in a dq / dk / dv image: 16 bytes per thread and step
+__device__ __forceinline__ void b8_zero_rows(bf16_t* base, int64_t ld, int r0, int nrows, int S, int tid) {
+    for (int e = tid; e < nrows * 16; e += 256) {
+        const int r = r0 + (e >> 4);
+        if (r < S) *reinterpret_cast<uint4*>(base + (int64_t)r * ld + (e & 15) * 8) = uint4{0u, 0u, 0u, 0u};
+    }
+}
+
+// VARLEN = false: the plain kernels (one Sq / Skv per launch).  VARLEN = true (self-attention, p.Sq ==
+// p.Skv == S): n_own = n_str = L[b], so sample b is computed as if launched alone at its own length; block counts and the Lp / Dp pitch
+// stay on the padded S, and own rows at or beyond L[b] are written as zeros.
+template <bool VARLEN>
+using b8_params = std::conditional_t<VARLEN, AttnBwdVarlenParams, AttnBwdParams>;
+
+template <bool DKDV, int B8_CB, bool VARLEN = false>
+__global__ __launch_bounds__(256, B8_CB == 1 ? (DKDV ? 3 : 4) : 2) void attn_bwd_d128_kernel(const b8_params<VARLEN> p) {
     constexpr int B8_OWN = 64 * B8_CB;
     __shared__ __attribute__((aligned(16))) char smem[2 * B8_ROWMAJ + 2 * B8_TRANS + 2 * B8_ROWS * 4];
     bf16_t* x0 = reinterpret_cast<bf16_t*>(smem);                        // streamed operand 0 (K | Q), row-major
@@ -53,9 +71,19 @@ __global__ __launch_bounds__(256, B8_CB == 1 ? (DKDV ? 3 : 4) : 2) void attn_bwd
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col = lane & 15, kg = lane >> 4;
-    const int n_own = DKDV ? p.Skv : p.Sq, n_str = DKDV ? p.Sq : p.Skv;
+    int n_own = DKDV ? p.Skv : p.Sq, n_str = DKDV ? p.Sq : p.Skv;
     int blk, h, b;
     xcd_local_bh((n_own + B8_OWN - 1) / B8_OWN, p.H, (int)gridDim.x, p.xcd_local, blk, h, b);
+    if constexpr (VARLEN) {
+        const int S = n_own;
+        n_own = n_str = b8_len(p.seq_lens, b, S);
+        if (blk * B8_OWN >= n_own) {        // every own row is padding: zeros, and out before the first barrier (uniform over the workgroup)
+            const int64_t off = (int64_t)b * p.bsdq + h * B8_HD;
+            b8_zero_rows((DKDV ? p.dk : p.dq) + off, p.lddq, blk * B8_OWN, B8_OWN, S, threadIdx.x);
+            if constexpr (DKDV) b8_zero_rows(p.dv + off, p.lddq, blk * B8_OWN, B8_OWN, S, threadIdx.x);
+            return;
+        }
+    }
     const int own0 = blk * B8_OWN + wave * (16 * B8_CB);
     const int64_t bh = (int64_t)b * p.H + h;
     const bf16_t* b0p = (DKDV ? p.k + (int64_t)b * p.bsk : p.q + (int64_t)b * p.bsq) + h * B8_HD;
@@ -241,13 +269,20 @@ __global__ __launch_bounds__(256, B8_CB == 1 ? (DKDV ? 3 : 4) : 2) void attn_bwd
 #pragma unroll
     for (int cb = 0; cb < B8_CB; ++cb) {
         const int orow = own0 + cb * 16 + col;
-        if (orow >= n_own) continue;
+        bool pad = false;                  // (VARLEN: a row between the sample's length and the padded one is written as zeros)
+        if constexpr (VARLEN) {
+            if (orow >= (DKDV ? p.Skv : p.Sq)) continue;
+            pad = orow >= n_own;
+        } else {
+            if (orow >= n_own) continue;
+        }
         bf16_t* o0 = (DKDV ? p.dk : p.dq) + (int64_t)b * p.bsdq + (int64_t)orow * p.lddq + h * B8_HD;
 #pragma unroll
         for (int db = 0; db < 8; ++db) {
             uint2 v;
             v.x = b8_pack(acc0[cb][db][0] * p.scale, acc0[cb][db][1] * p.scale);
             v.y = b8_pack(acc0[cb][db][2] * p.scale, acc0[cb][db][3] * p.scale);
+            if constexpr (VARLEN) { if (pad) v = uint2{0u, 0u}; }
             *reinterpret_cast<uint2*>(o0 + db * 16 + kg * 4) = v;
         }
         if constexpr (DKDV) {
@@ -257,6 +292,7 @@ __global__ __launch_bounds__(256, B8_CB == 1 ? (DKDV ? 3 : 4) : 2) void attn_bwd
                 uint2 v;
                 v.x = b8_pack(acc1[cb][db][0], acc1[cb][db][1]);
                 v.y = b8_pack(acc1[cb][db][2], acc1[cb][db][3]);
+                if constexpr (VARLEN) { if (pad) v = uint2{0u, 0u}; }
                 *reinterpret_cast<uint2*>(o1 + db * 16 + kg * 4) = v;
             }
         }
@@ -272,8 +308,8 @@ __global__ __launch_bounds__(256, B8_CB == 1 ? (DKDV ? 3 : 4) : 2) void attn_bwd
 // register 8 s + j; the A operand (the transposed tile) is read with that permutation as two 8-byte reads 8 queries apart.
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
-template <bool DKDV, int AHEAD = 0, bool LATE = false>
-__global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const AttnBwdParams p) {
+template <bool DKDV, int AHEAD = 0, bool LATE = false, bool VARLEN = false>
+__global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const b8_params<VARLEN> p) {
     constexpr int OWN = 128;
     // LDS: streamed tile row-major x 2 | transposed x0 (| transposed x1 | -L, -D of the tile's queries | the workgroup's own V rows)
     constexpr int OFF_T0 = 2 * B8_ROWMAJ, OFF_T1 = OFF_T0 + B8_TRANS, OFF_LD = OFF_T1 + B8_TRANS, OFF_XV = OFF_LD + 2 * B8_ROWS * 4;
@@ -288,9 +324,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const AttnBwd
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col = lane & 31, hi = lane >> 5;
-    const int n_own = DKDV ? p.Skv : p.Sq, n_str = DKDV ? p.Sq : p.Skv;
+    int n_own = DKDV ? p.Skv : p.Sq, n_str = DKDV ? p.Sq : p.Skv;
     int blk, h, b;
     xcd_local_bh((n_own + OWN - 1) / OWN, p.H, (int)gridDim.x, p.xcd_local, blk, h, b);
+    if constexpr (VARLEN) {
+        const int S = n_own;
+        n_own = n_str = b8_len(p.seq_lens, b, S);
+        if (blk * OWN >= n_own) {           // every own row is padding: zeros, and out before the first barrier (uniform over the workgroup)
+            const int64_t off = (int64_t)b * p.bsdq + h * B8_HD;
+            b8_zero_rows((DKDV ? p.dk : p.dq) + off, p.lddq, blk * OWN, OWN, S, threadIdx.x);
+            if constexpr (DKDV) b8_zero_rows(p.dv + off, p.lddq, blk * OWN, OWN, S, threadIdx.x);
+            return;
+        }
+    }
     const int own0 = blk * OWN + wave * 32;
     const int64_t bh = (int64_t)b * p.H + h;
     const bf16_t* s0p = (DKDV ? p.q + (int64_t)b * p.bsq : p.k + (int64_t)b * p.bsk) + h * B8_HD;
@@ -537,7 +583,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const AttnBwd
 
     // ---- store: acc[db][r] = (own row own0 + col, d = db * 32 + 8 (r >> 2) + 4 hi + (r & 3)): four consecutive d = 8 bytes
     const int orow = own0 + col;
-    if (orow < n_own) {
+    const bool pad = VARLEN && orow >= n_own;        // (VARLEN: a row between the sample's length and the padded one is written as zeros)
+    if (orow < (VARLEN ? (DKDV ? p.Skv : p.Sq) : n_own)) {
         bf16_t* o0 = (DKDV ? p.dk : p.dq) + (int64_t)b * p.bsdq + (int64_t)orow * p.lddq + h * B8_HD;
 #pragma unroll
         for (int db = 0; db < 4; ++db)
@@ -546,6 +593,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const AttnBwd
                 uint2 v;
                 v.x = pack2(f32x2_t{acc0[db][4 * q] * p.scale, acc0[db][4 * q + 1] * p.scale});
                 v.y = pack2(f32x2_t{acc0[db][4 * q + 2] * p.scale, acc0[db][4 * q + 3] * p.scale});
+                if constexpr (VARLEN) { if (pad) v = uint2{0u, 0u}; }
                 *reinterpret_cast<uint2*>(o0 + db * 32 + 8 * q + 4 * hi) = v;
             }
         if constexpr (DKDV) {
@@ -557,6 +605,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const AttnBwd
                     uint2 w;
                     w.x = pack2(f32x2_t{acc1[db][4 * q], acc1[db][4 * q + 1]});
                     w.y = pack2(f32x2_t{acc1[db][4 * q + 2], acc1[db][4 * q + 3]});
+                    if constexpr (VARLEN) { if (pad) w = uint2{0u, 0u}; }
                     *reinterpret_cast<uint2*>(o1 + db * 32 + 8 * q + 4 * hi) = w;
                 }
         }
@@ -564,11 +613,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const AttnBwd
 }
 
 // D[b, h, q] = sum_d O[q, d] dO[q, d]: one wave per (b, q) row, 16 lanes per head
-__global__ __launch_bounds__(256) void attn_bwd_delta128_kernel(const AttnBwdParams p, int B) {
+template <bool VARLEN>
+__global__ __launch_bounds__(256) void attn_bwd_delta128_kernel(const b8_params<VARLEN> p, int B) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= (int64_t)B * p.Sq) return;
     const int b = row / p.Sq, q = row % p.Sq;
+    if constexpr (VARLEN) {
+        if (q >= b8_len(p.seq_lens, b, p.Sq)) {       // a padding row (uniform over the wave): D = 0, o and dO are not read
+            if (lane < p.H) p.vec[((int64_t)b * p.H + lane) * p.Sq + q] = 0.f;
+            for (int h = 64 + lane; h < p.H; h += 64) p.vec[((int64_t)b * p.H + h) * p.Sq + q] = 0.f;
+            return;
+        }
+    }
     const bf16_t* o = p.o + (int64_t)b * p.bso + (int64_t)q * p.ldo;
     const bf16_t* d = p.d_o + (int64_t)b * p.bsdo + (int64_t)q * p.lddo;
     const int sub = lane & 15;
@@ -594,14 +651,21 @@ __global__ __launch_bounds__(256) void attn_bwd_delta128_kernel(const AttnBwdPar
 
 }  // namespace
 
-int attention_bwd_d128_launch(const AttnBwdParams& p, int B, hipStream_t s) {
+static int attention_bwd_d128_launch_any(const AttnBwdParams& p, int B, const int* seq_lens, hipStream_t s) {
     // every operand is addressed with 32-bit byte offsets from a per-(batch, head) base: checked for ALL of them -- q, dO, o, k, v and the
     // dq / dk / dv pitch -- and BEFORE the first launch (the delta kernel reads o and dO with the same arithmetic)
     auto fits = [](int64_t rows, int64_t ld) { return rows * ld * 2 < (1ll << 31); };
     const bool fits32 = fits(p.Sq, p.ldq) && fits(p.Sq, p.lddo) && fits(p.Sq, p.ldo) && fits(p.Skv, p.ldk) && fits(p.Skv, p.ldv) &&
                         fits(p.Sq > p.Skv ? p.Sq : p.Skv, p.lddq);
     ADVGRPO_CHECK(fits32, "attention_bwd (d128): rows * row stride must stay below 2^30 elements (32-bit byte offsets)");
-    hipLaunchKernelGGL(attn_bwd_delta128_kernel, dim3((unsigned)(((int64_t)B * p.Sq + 3) / 4)), dim3(256), 0, s, p, B);
+    const int64_t nq_chk = (int64_t)((p.Sq + 127) / 128) * p.H * B, nk_chk = (int64_t)((p.Skv + 63) / 64) * p.H * B;
+    ADVGRPO_CHECK(nq_chk < (1ll << 31) && nk_chk < (1ll << 31) && ((int64_t)B * p.Sq + 3) / 4 < (1ll << 31), "attention_bwd (d128): grid too large");
+    const dim3 gd((unsigned)(((int64_t)B * p.Sq + 3) / 4));
+    AttnBwdVarlenParams pv{};
+    static_cast<AttnBwdParams&>(pv) = p;
+    pv.seq_lens = seq_lens;
+    if (seq_lens) hipLaunchKernelGGL(attn_bwd_delta128_kernel<true>, gd, dim3(256), 0, s, pv, B);
+    else hipLaunchKernelGGL(attn_bwd_delta128_kernel<false>, gd, dim3(256), 0, s, p, B);
     ADVGRPO_LAUNCH_CHECK();
     // dQ: the 16x16 kernel with two own-row blocks per wave (227 registers, two waves per SIMD).  dK/dV: the 32x32 kernel (254 registers, two
     // waves per SIMD).  Same-box kernel times at 16 x 24 x 4224 (rocprofv3; scripts/probes/attn_bwd_d128_variants.sh):
@@ -620,6 +684,13 @@ int attention_bwd_d128_launch(const AttnBwdParams& p, int B, hipStream_t s) {
     const int64_t nq = (int64_t)((p.Sq + 64 * CBQ - 1) / (64 * CBQ)) * p.H * B, nk = (int64_t)((p.Skv + 64 * CBK - 1) / (64 * CBK)) * p.H * B;
     ADVGRPO_CHECK(nq < (1ll << 31) && nk < (1ll << 31), "attention_bwd (d128): grid too large");
     const dim3 gq((unsigned)((int64_t)((p.Sq + 127) / 128) * p.H * B)), gk((unsigned)((int64_t)((p.Skv + 127) / 128) * p.H * B));
+    if (seq_lens) {         // per-sample lengths: the product's variants (dQ 16x16 two blocks, dK/dV 32x32), same grids
+        hipLaunchKernelGGL((attn_bwd_d128_kernel<false, CBQ, true>), dim3((unsigned)nq), dim3(256), 0, s, pv);
+        ADVGRPO_LAUNCH_CHECK();
+        hipLaunchKernelGGL((attn_bwd_d128_w32_kernel<true, 0, false, true>), gk, dim3(256), 0, s, pv);
+        ADVGRPO_LAUNCH_CHECK();
+        return 0;
+    }
     if ((variant >> 4) & 1) hipLaunchKernelGGL((attn_bwd_d128_w32_kernel<false, 2, true>), gq, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((attn_bwd_d128_kernel<false, CBQ>), dim3((unsigned)nq), dim3(256), 0, s, p);
     ADVGRPO_LAUNCH_CHECK();
@@ -627,6 +698,11 @@ int attention_bwd_d128_launch(const AttnBwdParams& p, int B, hipStream_t s) {
     else hipLaunchKernelGGL((attn_bwd_d128_kernel<true, CBK>), dim3((unsigned)nk), dim3(256), 0, s, p);
     ADVGRPO_LAUNCH_CHECK();
     return 0;
+}
+
+int attention_bwd_d128_launch(const AttnBwdParams& p, int B, hipStream_t s) { return attention_bwd_d128_launch_any(p, B, nullptr, s); }
+int attention_bwd_d128_varlen_launch(const AttnBwdParams& p, int B, const int* seq_lens, hipStream_t s) {
+    return attention_bwd_d128_launch_any(p, B, seq_lens, s);
 }
 
 }  // namespace advgrpo

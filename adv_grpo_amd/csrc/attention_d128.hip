@@ -83,7 +83,13 @@ using d128_int = std::integral_constant<int, N>;
 
 }  // namespace
 
-__global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const AttnParams p) {
+// VARLEN = false is the plain kernel: one Sq / Skv for the launch, from the parameter block.
+// VARLEN = true (self-attention only, p.Sq == p.Skv == S, the padded length the grid is sized from): sample b is computed exactly as if it
+// had been launched alone at length L = seq_lens[b] clamped into [1, S] -- L stands wherever the plain kernel has p.Skv (tile count, the
+// clamp of the ragged last tile, the tail mask) or p.Sq (query clamp, store guards), the lse pitch stays p.Sq, and the rows L .. S - 1 of
+// o (and lse) are written as zeros.  L is wave-uniform (readfirstlane): it lives in an SGPR.
+template <bool VARLEN>
+__global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::conditional_t<VARLEN, AttnVarlenParams, AttnParams> p) {
     constexpr int HD = 128;
     extern __shared__ __attribute__((aligned(1024))) char smem[];      // K ring (4 x 16 KiB) | V ring (4 x 16 KiB) | 8 flag words
     int* const wg_flag = reinterpret_cast<int*>(smem + 2 * D128_SLOTS * D128_TILE);
@@ -94,16 +100,29 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const AttnPa
     int qblk, h, b;
     xcd_local_bh(p.nqb, p.H, p.nwg, p.xcd_local, qblk, h, b);
     const int q0 = qblk * D128_QB + wave * 32;
+    int L = 0;                                                         // (VARLEN only) the sample's own length
+    if constexpr (VARLEN) {
+        L = __builtin_amdgcn_readfirstlane(min(max(p.seq_lens[b], 1), p.Sq));
+        if (qblk * D128_QB >= L) {
+            // all 256 queries are padding: zero rows, and out before the first DMA (uniform over the workgroup: no barrier is skipped by a part of it)
+            for (int e = tid; e < D128_QB * 16; e += 512) {
+                const int qo = qblk * D128_QB + (e >> 4);
+                if (qo < p.Sq) *reinterpret_cast<uint4*>(p.o + (int64_t)b * p.bso + (int64_t)qo * p.ldo + h * HD + (e & 15) * 8) = uint4{0u, 0u, 0u, 0u};
+            }
+            if (p.lse && tid < D128_QB && qblk * D128_QB + tid < p.Sq) p.lse[((int64_t)b * p.H + h) * p.Sq + qblk * D128_QB + tid] = 0.f;
+            return;
+        }
+    }
     const bf16_t* qp = p.q + (int64_t)b * p.bsq + h * HD;
     const bf16_t* kp = p.k + (int64_t)b * p.bsk + h * HD;
     const bf16_t* vp = p.v + (int64_t)b * p.bsv + h * HD;
-    const int nt = (p.Skv + ATT_KB - 1) / ATT_KB;
+    const int nt = ((VARLEN ? L : p.Skv) + ATT_KB - 1) / ATT_KB;
 
     // ---- Q fragments (B operand of K Q^T: lane = query, 8 consecutive d at ks*16 + hi*8)
     bf16x8_t qf[8];
     {
         int qr = q0 + ql;
-        qr = qr < p.Sq ? qr : p.Sq - 1;
+        qr = qr < (VARLEN ? L : p.Sq) ? qr : (VARLEN ? L : p.Sq) - 1;
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks)
             qf[ks] = *reinterpret_cast<const bf16x8_t*>(qp + (int64_t)qr * p.ldq + ks * 16 + hi * 8);
@@ -116,7 +135,7 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const AttnPa
     const int lrow = lane >> 4, slot16 = lane & 15;
     uint32_t k_lo[2], v_lo[2], k_last[2], v_last[2];
     {
-        const int rmax = p.Skv - 1 - (nt - 1) * ATT_KB;
+        const int rmax = (VARLEN ? L : p.Skv) - 1 - (nt - 1) * ATT_KB;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int R = (wave + 8 * i) * 4 + lrow;
@@ -234,13 +253,13 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const AttnPa
         return d128_max3(a, bb, bb);
     };
     auto mask_tail = [&](f32x16 (&sc)[2], int kv0) __attribute__((always_inline)) {
-        if (kv0 + ATT_KB > p.Skv) {
+        if (kv0 + ATT_KB > (VARLEN ? L : p.Skv)) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = kv0 + kb * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
-                    if (key >= p.Skv) sc[kb][r] = -INFINITY;
+                    if (key >= (VARLEN ? L : p.Skv)) sc[kb][r] = -INFINITY;
                 }
         }
     };
@@ -421,7 +440,11 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const AttnPa
     // whole 256-byte rows, 16 bytes per lane
     const float inv = l > 0.f ? 1.0f / l : 0.f;
     const int qi = q0 + ql;
-    if (p.lse && hi == 0 && qi < p.Sq) p.lse[((int64_t)b * p.H + h) * p.Sq + qi] = m_ref + __builtin_amdgcn_logf(l);
+    if constexpr (VARLEN) {
+        if (p.lse && hi == 0 && qi < p.Sq) p.lse[((int64_t)b * p.H + h) * p.Sq + qi] = qi < (VARLEN ? L : p.Sq) ? m_ref + __builtin_amdgcn_logf(l) : 0.f;
+    } else {
+        if (p.lse && hi == 0 && qi < p.Sq) p.lse[((int64_t)b * p.H + h) * p.Sq + qi] = m_ref + __builtin_amdgcn_logf(l);
+    }
     char* ob = smem + wave * 8192;
 #pragma unroll
     for (int db = 0; db < 4; ++db)
@@ -439,7 +462,11 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const AttnPa
         const int r = ps * 4 + (lane >> 4), c = lane & 15;
         const uint4 v = *reinterpret_cast<const uint4*>(ob + r * 256 + ((c ^ (r & 15)) << 4));
         const int qo = q0 + r;
-        if (qo < p.Sq) *reinterpret_cast<uint4*>(p.o + (int64_t)b * p.bso + (int64_t)qo * p.ldo + h * HD + c * 8) = v;
+        if constexpr (VARLEN) {
+            if (qo < p.Sq) *reinterpret_cast<uint4*>(p.o + (int64_t)b * p.bso + (int64_t)qo * p.ldo + h * HD + c * 8) = qo < (VARLEN ? L : p.Sq) ? v : uint4{0u, 0u, 0u, 0u};
+        } else {
+            if (qo < p.Sq) *reinterpret_cast<uint4*>(p.o + (int64_t)b * p.bso + (int64_t)qo * p.ldo + h * HD + c * 8) = v;
+        }
     }
 }
 
@@ -451,8 +478,10 @@ int attention_d128_fallbacks(unsigned long long* out, int reset) {
     return 0;
 }
 
-int attention_fwd_d128_launch(const AttnParams& p_in, int B, hipStream_t s) {
-    AttnParams p = p_in;
+static int attention_fwd_d128_launch_any(const AttnParams& p_in, int B, const int* seq_lens, hipStream_t s) {
+    AttnVarlenParams p{};
+    static_cast<AttnParams&>(p) = p_in;
+    p.seq_lens = seq_lens;
     p.nqb = (p.Sq + D128_QB - 1) / D128_QB;
     const int64_t nwg = (int64_t)p.nqb * p.H * B;
     ADVGRPO_CHECK(nwg < (1ll << 31), "attention: grid too large");
@@ -461,12 +490,19 @@ int attention_fwd_d128_launch(const AttnParams& p_in, int B, hipStream_t s) {
     ADVGRPO_CHECK((int64_t)ATT_KB * p.ldk * 2 < (1ll << 31) && (int64_t)ATT_KB * p.ldv * 2 < (1ll << 31), "attention: row pitch too large");
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_fwd_d128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, D128_LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_fwd_d128_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, D128_LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_fwd_d128_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, D128_LDS);
         attr_set = true;
     }
-    hipLaunchKernelGGL(attention_fwd_d128_kernel, dim3((unsigned)p.nwg), dim3(512), D128_LDS, s, p);
+    if (seq_lens) hipLaunchKernelGGL(attention_fwd_d128_kernel<true>, dim3((unsigned)p.nwg), dim3(512), D128_LDS, s, p);
+    else hipLaunchKernelGGL(attention_fwd_d128_kernel<false>, dim3((unsigned)p.nwg), dim3(512), D128_LDS, s, static_cast<const AttnParams&>(p));
     ADVGRPO_LAUNCH_CHECK();
     return 0;
+}
+
+int attention_fwd_d128_launch(const AttnParams& p, int B, hipStream_t s) { return attention_fwd_d128_launch_any(p, B, nullptr, s); }
+int attention_fwd_d128_varlen_launch(const AttnParams& p, int B, const int* seq_lens, hipStream_t s) {
+    return attention_fwd_d128_launch_any(p, B, seq_lens, s);
 }
 
 }  // namespace advgrpo

@@ -65,15 +65,22 @@ def velocity(pipe, latents, t, B, tem_pe, tem_ppe, mods, ctx_rows, do_cfg, joint
                 ent = sides[threading.get_ident()] = (main, torch.cuda.Stream(device=device))
         side = ent[1]
         Nt = tem_pe.shape[1]
+        # a prompt mask (Qwen-Image: joint_attention_kwargs["encoder_hidden_states_mask"], [2 B, Nt]) is split like the embeddings
+        mask = (joint_attention_kwargs or {}).get("encoder_hidden_states_mask")
+        half = (lambda lo, hi: {}) if mask is None else \
+            (lambda lo, hi: {"joint_attention_kwargs": dict(joint_attention_kwargs, encoder_hidden_states_mask=mask[lo:hi])})
+        # the modulation rows: one per sample of the CFG batch (SD3: the pooled embedding enters them), or ONE shared row (Qwen-Image:
+        # the timestep alone), which serves both halves as it is -- slicing it [B:] would hand the conditional half an empty tensor
+        mods_u, mods_t = (mods[:B], mods[B:]) if mods.shape[0] == 2 * B else (mods, mods)
         ready = torch.cuda.Event()
         ready.record(main)
         side.wait_event(ready)
         with torch.cuda.stream(side):
             vt = pipe.transformer(hidden_states=latents, timestep=t.expand(B), encoder_hidden_states=tem_pe[B:], pooled_projections=tem_ppe[B:],
-                                  return_dict=False, mods=mods[B:], context=ctx_rows[B * Nt:])[0]
+                                  return_dict=False, mods=mods_t, context=ctx_rows[B * Nt:], **half(B, 2 * B))[0]
         latents.record_stream(side)
         vu = pipe.transformer(hidden_states=latents, timestep=t.expand(B), encoder_hidden_states=tem_pe[:B], pooled_projections=tem_ppe[:B],
-                              return_dict=False, mods=mods[:B], context=ctx_rows[:B * Nt])[0]
+                              return_dict=False, mods=mods_u, context=ctx_rows[:B * Nt], **half(0, B))[0]
         main.wait_stream(side)
         vt.record_stream(main)
         return vu, vt

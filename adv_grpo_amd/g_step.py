@@ -14,7 +14,7 @@ from .diffusers_patch.sd3_sde_with_logprob import sde_step_cfg
 
 @torch.no_grad()
 def micro_step(model, scheduler, sample, j, embeds, pooled_embeds, old_log_prob, advantages, *, guidance_scale,
-               noise_level, adv_clip_max, clip_range, loss_scale=1.0, step_index=None, beta=0.0, sde_type="cps"):
+               noise_level, adv_clip_max, clip_range, loss_scale=1.0, step_index=None, beta=0.0, sde_type="cps", embeds_mask=None):
     """sample: dict with latents / next_latents [G,T,16,h,w], timesteps [G,T].  embeds / pooled: CFG-concatenated
     (negative first, TP:1084-1091).  Accumulates into model.grads; returns the diagnostics of TP:1132-1162.
     step_index: scheduler index of timestep j, carried on the host by the caller (the rollout knows it); without it the
@@ -25,13 +25,16 @@ def micro_step(model, scheduler, sample, j, embeds, pooled_embeds, old_log_prob,
     sde_type: the step the rollout recorded its log-probs with -- "cps" (Flow-CPS) or "sde" (Flow-SDE, SDE:13-73): the replay forward, the
     reference mean and both backward entries follow it.  `scheduler.sigmas` must be the table the rollout recorded with (Trainer.g_step
     re-installs it with set_timesteps(sample.num_steps) before the first micro-step): `step_index` indexes it, and Flow-SDE's sigma_max
-    = sigmas[1] depends on the number of steps as well."""
+    = sigmas[1] depends on the number of steps as well.
+    embeds_mask: the prompt mask of `embeds` ([2 G, Nt], same row order; Qwen-Image), handed to forward_train as encoder_hidden_states_mask
+    and to the reference forward; None: nothing is passed."""
     lib = _lib.load()
     x = sample["latents"][:, j].contiguous()
     nxt = sample["next_latents"][:, j].contiguous()
     ts = sample["timesteps"][:, j]
     G = x.shape[0]
-    v, ctx = model.forward_train(torch.cat([x, x]), torch.cat([ts, ts]).float(), embeds, pooled_embeds)
+    mask_kw = {} if embeds_mask is None else {"encoder_hidden_states_mask": embeds_mask}
+    v, ctx = model.forward_train(torch.cat([x, x]), torch.cat([ts, ts]).float(), embeds, pooled_embeds, **mask_kw)
     vu, vt = v[:G].contiguous(), v[G:].contiguous()
     if step_index is None:
         step_index = scheduler.index_for_timestep(float(ts[0]))
@@ -39,7 +42,8 @@ def micro_step(model, scheduler, sample, j, embeds, pooled_embeds, old_log_prob,
                                         want_mean=False, step_index=step_index, sde_type=sde_type)
     mean_ref = None
     if beta > 0:
-        v_ref = model.forward_reference(torch.cat([x, x]), torch.cat([ts, ts]).float(), embeds, pooled_embeds)
+        v_ref = model.forward_reference(torch.cat([x, x]), torch.cat([ts, ts]).float(), embeds, pooled_embeds,
+                                        **({} if embeds_mask is None else {"joint_attention_kwargs": mask_kw}))
         _, _, _, mean_ref, _ = sde_step_cfg(scheduler, v_ref[:G].contiguous(), v_ref[G:].contiguous(), guidance_scale, None, x,
                                             noise_level, prev_sample=nxt, want_mean=True, step_index=step_index, sde_type=sde_type)
     scal, dlp = losses.grpo_loss(log_prob, old_log_prob, advantages, adv_clip_max, clip_range)

@@ -293,9 +293,10 @@ class SD3TransformerLoRA(SD3Transformer2DModel):
         return SD3Transformer2DModel.__call__(self, *a, **kw)
 
     @torch.no_grad()
-    def forward_reference(self, hidden_states, timestep, encoder_hidden_states, pooled_projections):
+    def forward_reference(self, hidden_states, timestep, encoder_hidden_states, pooled_projections, joint_attention_kwargs=None):
         """The forward under PEFT's `disable_adapter()` (TP:1105-1108: the reference policy of the KL term): the rollout
-        forward on the base weights of the adapted projections.  Returns v [B,16,h,w] bf16."""
+        forward on the base weights of the adapted projections.  Returns v [B,16,h,w] bf16.  joint_attention_kwargs goes to the
+        forward as it is (the Qwen-Image model reads its prompt mask there; this model ignores the key)."""
         saved = []
         for i, b in enumerate(self.blocks):
             for gk, (base, _) in self._base_T[i].items():
@@ -318,7 +319,8 @@ class SD3TransformerLoRA(SD3Transformer2DModel):
                     f8_saved[(i, gk)] = self.fp8[(i, gk)]
                     self.fp8[(i, gk)] = self._fp8_base[(i, gk)]
         try:
-            (v,) = self._base_forward(hidden_states, timestep, encoder_hidden_states, pooled_projections)
+            (v,) = self._base_forward(hidden_states, timestep, encoder_hidden_states, pooled_projections,
+                                      **({} if joint_attention_kwargs is None else {"joint_attention_kwargs": joint_attention_kwargs}))
         finally:
             self.lora_ext = ext
             for b, kv in saved:
@@ -329,8 +331,9 @@ class SD3TransformerLoRA(SD3Transformer2DModel):
 
     # ------------------------------------------------------------------ forward with saved activations
     @torch.no_grad()
-    def forward_train(self, hidden_states, timestep, encoder_hidden_states, pooled_projections):
-        """Same arithmetic as __call__, keeping what backward() needs.  Returns (v [B,16,h,w] bf16, ctx)."""
+    def forward_train(self, hidden_states, timestep, encoder_hidden_states, pooled_projections, encoder_hidden_states_mask=None):
+        """Same arithmetic as __call__, keeping what backward() needs.  Returns (v [B,16,h,w] bf16, ctx).  (encoder_hidden_states_mask:
+        the Qwen-Image model's keyword; SD3 prompts have one length and the argument is ignored.)"""
         cfg, w = self.cfg, self.w
         D, H = cfg.dim, cfg.num_heads
         B, C, h, wd = hidden_states.shape

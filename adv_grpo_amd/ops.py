@@ -237,8 +237,15 @@ def attention_bias(q, k, v, num_heads, bias, scale=1.0, causal=False, out=None):
     return out
 
 
-def attention(q, k, v, num_heads, scale=None, causal=False, out=None, lse=None):
-    """q [B,Sq,H*D], k/v [B,Skv,H*D] bf16 views (last dim contiguous, any row/batch pitch) -> [B,Sq,H*D]."""
+def _check_seq_lens(seq_lens, B, Sq, Skv, causal):
+    assert Sq == Skv and not causal, "seq_lens: self-attention over one padded length, non-causal"
+    assert seq_lens.dtype == torch.int32 and seq_lens.is_cuda and seq_lens.is_contiguous() and tuple(seq_lens.shape) == (B,)
+
+
+def attention(q, k, v, num_heads, scale=None, causal=False, out=None, lse=None, seq_lens=None):
+    """q [B,Sq,H*D], k/v [B,Skv,H*D] bf16 views (last dim contiguous, any row/batch pitch) -> [B,Sq,H*D].
+    seq_lens (int32 [B] on the device; head dim 128, Sq == Skv): sample b is computed as if launched alone at length seq_lens[b]
+    (clamped into [1, S]); rows beyond it are never read and are written as zeros in out / lse."""
     lib = _lib.load()
     B, Sq, HD = q.shape
     Skv = k.shape[1]
@@ -248,6 +255,13 @@ def attention(q, k, v, num_heads, scale=None, causal=False, out=None, lse=None):
         out = torch.empty(B, Sq, HD, dtype=torch.bfloat16, device=q.device)
     if scale is None:
         scale = D ** -0.5
+    if seq_lens is not None:
+        _check_seq_lens(seq_lens, B, Sq, Skv, causal)
+        _lib.check(lib.advgrpo_attention_fwd_varlen(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), q.stride(1), k.stride(1), v.stride(1),
+            out.stride(1), q.stride(0), k.stride(0), v.stride(0), out.stride(0), B, num_heads, Sq, D,
+            float(scale), seq_lens.data_ptr(), lse.data_ptr() if lse is not None else None, _lib.stream_ptr()))
+        return out
     _lib.check(lib.advgrpo_attention_fwd(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), q.stride(1), k.stride(1), v.stride(1),
         out.stride(1), q.stride(0), k.stride(0), v.stride(0), out.stride(0), B, num_heads, Sq, Skv, D,
@@ -263,9 +277,41 @@ def attention_fallback_count(reset=True):
     return n.value
 
 
-def attention_bwd(q, k, v, o, d_o, lse, num_heads, dq, dk, dv, scale=None):
+_MASK_DTYPES = {torch.bool: _lib.U8, torch.uint8: _lib.U8, torch.int32: _lib.I32, torch.int64: _lib.I64}
+_bad_rows = {}          # device -> int32 counter of mask rows that were not right-padded prefixes
+
+
+def mask_to_seq_lens(mask, base, out=None):
+    """mask [B, Nt] (bool, uint8, int32 or int64; non-zero = valid) -> int32 [B]: base + the number of leading non-zero entries of each row.
+    One launch, no host sync.  A row that is no right-padded prefix (a non-zero behind a zero, or no leading non-zero) is counted on the
+    device: read with bad_count()."""
+    assert mask.dim() == 2 and mask.is_cuda and mask.dtype in _MASK_DTYPES, (mask.shape, mask.dtype)
+    mask = mask.contiguous()
+    B, Nt = mask.shape
+    if out is None:
+        out = torch.empty(B, dtype=torch.int32, device=mask.device)
+    bad = _bad_rows.get(mask.device)
+    if bad is None:
+        bad = _bad_rows[mask.device] = torch.zeros(1, dtype=torch.int32, device=mask.device)
+    _lib.check(_lib.load().advgrpo_mask_to_seq_lens(mask.data_ptr(), _MASK_DTYPES[mask.dtype], out.data_ptr(), B, Nt, int(base),
+                                                    bad.data_ptr(), _lib.stream_ptr()))
+    return out
+
+
+def bad_count(reset=True):
+    """Mask rows mask_to_seq_lens has seen since the last reset that were not right-padded prefixes (synchronises)."""
+    n = 0
+    for t in _bad_rows.values():
+        n += int(t.item())
+        if reset:
+            t.zero_()
+    return n
+
+
+def attention_bwd(q, k, v, o, d_o, lse, num_heads, dq, dk, dv, scale=None, seq_lens=None):
     """Gradients of ops.attention (head dim 64 or 128).  q,k,v,o,d_o: [B,S,H*hd] bf16 views; lse f32 [B,H,Sq] from the forward;
-    dq/dk/dv: bf16 views of ONE packed buffer (same row / batch pitch)."""
+    dq/dk/dv: bf16 views of ONE packed buffer (same row / batch pitch).  seq_lens as in ops.attention (the forward must have had the
+    same): gradient rows beyond a sample's length are written as zeros."""
     lib = _lib.load()
     B, Sq, HD = q.shape
     Skv = k.shape[1]
@@ -274,6 +320,14 @@ def attention_bwd(q, k, v, o, d_o, lse, num_heads, dq, dk, dv, scale=None):
         scale = D ** -0.5
     assert dq.stride(1) == dk.stride(1) == dv.stride(1) and dq.stride(0) == dk.stride(0) == dv.stride(0)
     work = torch.empty(B, num_heads, (Sq + 31) // 32, 64, dtype=torch.float32, device=q.device)    # (-L/c | -D) per 32 queries
+    if seq_lens is not None:
+        _check_seq_lens(seq_lens, B, Sq, Skv, False)
+        _lib.check(lib.advgrpo_attention_bwd_varlen(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), work.data_ptr(),
+            dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), q.stride(1), k.stride(1), v.stride(1), o.stride(1),
+            d_o.stride(1), dq.stride(1), q.stride(0), k.stride(0), v.stride(0), o.stride(0), d_o.stride(0), dq.stride(0),
+            B, num_heads, Sq, D, float(scale), seq_lens.data_ptr(), _lib.stream_ptr()))
+        return dq, dk, dv
     _lib.check(lib.advgrpo_attention_bwd(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), d_o.data_ptr(), lse.data_ptr(), work.data_ptr(),
         dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), q.stride(1), k.stride(1), v.stride(1), o.stride(1),

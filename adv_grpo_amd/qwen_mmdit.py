@@ -12,11 +12,14 @@ pooled_projections, ..., return_dict=False)[0]`` -- so that ``pipeline_with_logp
     timestep / 1000 and the model's Timesteps(scale=1000) multiplies it back: the same sinusoid argument;
   * ``pooled_projections`` is accepted and ignored (Qwen-Image conditions on the timestep only).
 Weights are loaded from a diffusers-named state dict (oracle/qwen_mmdit.py has the restated architecture, PARITY UNPINNED).
-Assumption: every prompt of a batch -- the negative and the positive half of the CFG batch included -- is handed over at ONE text length
-N_txt and no ``encoder_hidden_states_mask`` is applied: QwenImagePipeline pads to the longest prompt and masks the padding keys; here the caller
-(qwen_text_encoder.py, the trainer's data path) pads with the tokenizer's pad token and the padding positions attend and are attended like any other token.
-scripts/verify_against_diffusers.py pins the restatement against diffusers' masked forward on ragged lengths by running the shorter prompt unpadded here
-(what the mask makes of it there).
+Prompt mask: QwenImagePipeline pads a batch to its longest prompt and masks the padding keys.  ``encoder_hidden_states_mask`` ([B, N_txt],
+right-padded; also read from ``joint_attention_kwargs["encoder_hidden_states_mask"]``, the way the rollout functions carry extra arguments) does
+the same here: one ops.mask_to_seq_lens launch gives the per-sample joint lengths N_img + text_len[b] on the device, and every block's attention
+runs with them (advgrpo_attention_fwd_varlen: sample b exactly as if launched alone at its own length; the attention rows of the padding
+positions come back as zeros).  Every other op of the forward is row-wise, so nothing else changes and the image output does not depend on what
+the padding positions hold.  WITHOUT a mask every prompt of a batch -- the negative and the positive half of the CFG batch included --
+is taken at ONE text length N_txt: the caller pads with the tokenizer's pad token and the padding positions attend and are attended like any
+other token.  scripts/verify_against_diffusers.py pins the restatement against diffusers' masked forward on ragged lengths.
 
 Data layout in HBM (bf16), B = batch incl. the CFG halves, S = N_img + N_txt, D = 3072, 24 heads x 128:
   x [B*N_img, D], c [B*N_txt, D] residual streams, updated in place by the out-projection / FF2 epilogues
@@ -171,8 +174,10 @@ class QwenImageTransformer2DModel:
 
     @torch.no_grad()
     def __call__(self, hidden_states, timestep, encoder_hidden_states, pooled_projections=None, joint_attention_kwargs=None,
-                 return_dict=False, out_dtype=None, return_intermediates=False, mods=None, context=None):
+                 return_dict=False, out_dtype=None, return_intermediates=False, mods=None, context=None, encoder_hidden_states_mask=None):
         cfg, w = self.cfg, self.w
+        if encoder_hidden_states_mask is None and joint_attention_kwargs:
+            encoder_hidden_states_mask = joint_attention_kwargs.get("encoder_hidden_states_mask")
         D, H, hd = cfg.dim, cfg.num_heads, cfg.head_dim
         B, C, h, wd = hidden_states.shape
         hh, ww = h // cfg.patch_size, wd // cfg.patch_size
@@ -194,6 +199,7 @@ class QwenImageTransformer2DModel:
         if return_intermediates:
             inter.update(x0=x.view(B, Ni, D).clone(), c0=c.view(B, Nt, D).clone(), temb=temb.expand(B, -1).clone())
         rope = self._rope(hh, ww, Nt)
+        seq_lens = joint_seq_lens(encoder_hidden_states_mask, B, Ni, Nt, dev)
 
         def mod(key, j):
             o = self.mod_off[key] + j * D
@@ -232,7 +238,7 @@ class QwenImageTransformer2DModel:
             # --- joint attention: fused QKV projections scattered into the joint buffer, QK-norm + rotary in place, attention
             linears(i, b, [(nx, "qkv", dict(out=qkv, seg=(Ni, S, 0))), (nc, "cqkv", dict(out=qkv, seg=(Nt, S, Ni)))])
             ops.qk_norm_rope(qkv, S, Ni, 2 * H, hd, b["rms_x"], b["rms_c"], H, rope=rope, eps=1e-6)
-            ops.attention(qkv3[:, :, :D], qkv3[:, :, D:2 * D], qkv3[:, :, 2 * D:], H, out=att)
+            ops.attention(qkv3[:, :, :D], qkv3[:, :, D:2 * D], qkv3[:, :, 2 * D:], H, out=att, seq_lens=seq_lens)
             if f8 is not None:
                 ops.quant_fp8_rows(att2d, out=q_n, split=(Ni, S))
                 outs = [(q_n.rows(0, Mi), "out", dict(gate=mod(kx, 2), gate_rows=Ni, residual=x, out=x)),
@@ -264,6 +270,17 @@ class QwenImageTransformer2DModel:
         if return_intermediates:
             return (out,), inter
         return (out,)
+
+
+def joint_seq_lens(mask, B, Ni, Nt, device):
+    """encoder_hidden_states_mask [B, Nt] (or None) -> int32 [B] joint lengths Ni + text_len[b] on the device (None without a mask)."""
+    if mask is None:
+        return None
+    assert tuple(mask.shape) == (B, Nt), (tuple(mask.shape), (B, Nt))
+    mask = mask.to(device)
+    if mask.dtype not in (torch.bool, torch.uint8, torch.int32, torch.int64):
+        mask = mask != 0
+    return ops.mask_to_seq_lens(mask, Ni)
 
 
 def flops_per_sample_forward(cfg, n_img, n_txt):

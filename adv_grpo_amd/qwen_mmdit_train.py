@@ -27,7 +27,7 @@ import torch
 from . import ops
 from .ema import EMAModuleWrapper
 from .mmdit_train import RANK, RPAD, SD3TransformerLoRA, _Adapter
-from .qwen_mmdit import QwenImageTransformer2DModel
+from .qwen_mmdit import QwenImageTransformer2DModel, joint_seq_lens
 
 TARGETS = ("to_q", "to_k", "to_v", "to_out.0", "add_q_proj", "add_k_proj", "add_v_proj", "to_add_out")
 GROUPS = {"qkv": ("to_q", "to_k", "to_v"), "cqkv": ("add_q_proj", "add_k_proj", "add_v_proj"), "out": ("to_out.0",), "cout": ("to_add_out",)}
@@ -114,11 +114,11 @@ class QwenImageTransformerLoRA(QwenImageTransformer2DModel):
         self.w["proj_out.wT"] = T(self.w["proj_out.w"])
 
     # ------------------------------------------------------------------ one block: the launches of __call__ (bf16 or fp8 Linears)
-    def _block(self, i, x, c, mods, rope, B, Ni, Nt, save=None, keep_att=None, att_kept=None):
+    def _block(self, i, x, c, mods, rope, B, Ni, Nt, save=None, keep_att=None, att_kept=None, seq_lens=None):
         """In place on x [B * Ni, D], c [B * Nt, D].  `save` (a dict) receives what the block's backward needs -- the RE-RUN inside
         backward(): it takes the attention output and log-sum-exp the first run kept (`att_kept`) instead of launching the attention
         again, and stops after the feed-forward's first Linear (nothing differentiates the block's output).  `keep_att` (a list):
-        the first run appends (att, lse)."""
+        the first run appends (att, lse).  `seq_lens`: the per-sample joint lengths of a masked batch (qwen_mmdit.joint_seq_lens)."""
         cfg, b = self.cfg, self.blocks[i]
         D, H, hd = cfg.dim, cfg.num_heads, cfg.head_dim
         S, Mi, Mt = Ni + Nt, B * Ni, B * Nt
@@ -160,7 +160,7 @@ class QwenImageTransformerLoRA(QwenImageTransformer2DModel):
         else:
             att = torch.empty(B, S, D, dtype=bf16, device=dev)
             lse = torch.empty(B, H, S, dtype=torch.float32, device=dev) if (save is not None or keep_att is not None) else None
-            ops.attention(qkv3[:, :, :D], qkv3[:, :, D:2 * D], qkv3[:, :, 2 * D:], H, out=att, lse=lse)
+            ops.attention(qkv3[:, :, :D], qkv3[:, :, D:2 * D], qkv3[:, :, 2 * D:], H, out=att, lse=lse, seq_lens=seq_lens)
             if keep_att is not None:
                 keep_att.append((att, lse))
         att2d = att.view(B * S, D)
@@ -199,8 +199,11 @@ class QwenImageTransformerLoRA(QwenImageTransformer2DModel):
 
     # ------------------------------------------------------------------ forward keeping one checkpoint per block
     @torch.no_grad()
-    def forward_train(self, hidden_states, timestep, encoder_hidden_states, pooled_projections=None):
-        """Same arithmetic as __call__ (bf16 or fp8 Linears).  Returns (v [B,16,h,w] bf16, ctx)."""
+    def forward_train(self, hidden_states, timestep, encoder_hidden_states, pooled_projections=None, encoder_hidden_states_mask=None):
+        """Same arithmetic as __call__ (bf16 or fp8 Linears).  Returns (v [B,16,h,w] bf16, ctx).  With encoder_hidden_states_mask the
+        per-sample lengths are kept in ctx: the recomputation and the attention backward of backward() use them, the padding text rows
+        carry exactly zero gradient through every (row-wise) op of the chain, and the adapter-gradient GEMMs, which sum over all rows,
+        get zero from them."""
         cfg, w = self.cfg, self.w
         D = cfg.dim
         B, C, h, wd = hidden_states.shape
@@ -212,11 +215,12 @@ class QwenImageTransformerLoRA(QwenImageTransformer2DModel):
         mods = mods.expand(B, -1) if mods.shape[0] == 1 else mods
         c = self.embed_context(encoder_hidden_states)
         rope = self._rope(hh, ww, Nt)
-        ctx = {"B": B, "Ni": Ni, "Nt": Nt, "h": h, "w": wd, "mods": mods, "rope": rope, "x_in": [], "c_in": [], "att": []}
+        seq_lens = joint_seq_lens(encoder_hidden_states_mask, B, Ni, Nt, x.device)
+        ctx = {"B": B, "Ni": Ni, "Nt": Nt, "h": h, "w": wd, "mods": mods, "rope": rope, "x_in": [], "c_in": [], "att": [], "seq_lens": seq_lens}
         for i in range(cfg.num_layers):
             ctx["x_in"].append(x.clone())
             ctx["c_in"].append(c.clone())
-            self._block(i, x, c, mods, rope, B, Ni, Nt, keep_att=ctx["att"] if self.keep_attention else None)
+            self._block(i, x, c, mods, rope, B, Ni, Nt, keep_att=ctx["att"] if self.keep_attention else None, seq_lens=seq_lens)
         ctx["x_final"] = x
         o = self.mod_off[("out",)]
         nx = ops.layernorm_mod(x, scale=mods[:, o:o + D], shift=mods[:, o + D:o + 2 * D], rows_per_batch=Ni)
@@ -249,7 +253,8 @@ class QwenImageTransformerLoRA(QwenImageTransformer2DModel):
             b, s = self.blocks[i], {}
             kx, kc = ("x", i), ("c", i)
             x_in, c_in = ctx["x_in"][i], ctx["c_in"][i]
-            self._block(i, x_in.clone(), c_in.clone(), mods, rope, B, Ni, Nt, save=s, att_kept=ctx["att"][i] if ctx["att"] else None)
+            self._block(i, x_in.clone(), c_in.clone(), mods, rope, B, Ni, Nt, save=s, att_kept=ctx["att"][i] if ctx["att"] else None,
+                        seq_lens=ctx["seq_lens"])
             # ---- MLPs (the text-stream GEMMs ride in the launches of their image-stream twins, as in the forward)
             dyg, dcyg = ops.gate_mul(dx, mod(kx, 5), Ni), ops.gate_mul(dc, mod(kc, 5), Nt)
             dpres = ops.gemm_grouped([ops.gemm_desc(dyg, b["ff2.wT"], act="dgelu_tanh", aux_in=s["pre"]),
@@ -269,7 +274,7 @@ class QwenImageTransformerLoRA(QwenImageTransformer2DModel):
             dqkv = torch.empty(B * S, 3 * D, dtype=bf16, device=dev)
             d3 = dqkv.view(B, S, 3 * D)
             ops.attention_bwd(q3[:, :, :D], q3[:, :, D:2 * D], q3[:, :, 2 * D:], s["att"], datt.view(B, S, D), s["lse"], H,
-                              d3[:, :, :D], d3[:, :, D:2 * D], d3[:, :, 2 * D:])
+                              d3[:, :, :D], d3[:, :, D:2 * D], d3[:, :, 2 * D:], seq_lens=ctx["seq_lens"])
             ops.qk_norm_rope_bwd(dqkv, s["qkv"], s["rs"], S, Ni, 2 * H, hd, b["rms_x"], b["rms_c"], H, rope=rope)
             dnx, dnc = ops.gemm_grouped([ops.gemm_desc(dqkv, b["qkv.wT"], a_seg=(Ni, S, 0), M=B * Ni),
                                          ops.gemm_desc(dqkv, b["cqkv.wT"], a_seg=(Nt, S, Ni), M=B * Nt)])

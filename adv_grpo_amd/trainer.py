@@ -331,6 +331,8 @@ class Trainer:
         if hasattr(self.data, "prefetch"):          # decode the reference images of the epoch's groups during sampling
             self.data.prefetch(plan[:2])
 
+        neg_mask = getattr(self.data, "neg_mask", None)
+
         def inputs(i):
             idx = plan[i]
             if hasattr(self.data, "prefetch") and i + 2 < nb:
@@ -351,13 +353,25 @@ class Trainer:
             sde_kw = {"sde_type": c.sample.sde_type}
 
         def rollout(i, idx, pe, ppe, ref, prompts):
+            # optional pass-through of a prompt mask (Qwen-Image: right-padded prompts of different lengths).  A data source that has
+            # `prompt_mask(idx)` -> [1, Nt] and `neg_mask` [1, Nt] gets its masks to the transformer: to the rollout through
+            # joint_attention_kwargs, rows in the order of the CFG batch (cfg_embeddings: negative rows first), and to the replay through
+            # the sample's "prompt_embeds_mask".  Without them nothing changes.
+            pm = self.data.prompt_mask(idx) if (neg_mask is not None and hasattr(self.data, "prompt_mask")) else None
+            mask_kw = {}
+            if pm is not None:
+                if rollout_fn is not pipeline_with_logprob_random:
+                    raise NotImplementedError("a prompt mask with sample.branch_rollout: the branching rollout changes its batch at the branch step")
+                pm = pm.to(self.device).repeat(G, 1)
+                rows = torch.cat([neg_mask.to(self.device).repeat(G, 1), pm]) if c.sample.guidance_scale > 1 else pm
+                mask_kw = {"joint_attention_kwargs": {"encoder_hidden_states_mask": rows}}
             images, lats, lps, tss = rollout_fn(
                 self.pipe, prompt_embeds=pe, pooled_prompt_embeds=ppe, negative_prompt_embeds=neg_pe,
                 negative_pooled_prompt_embeds=neg_ppe, num_inference_steps=c.sample.num_steps,
                 guidance_scale=c.sample.guidance_scale, output_type="pt", height=c.resolution, width=c.resolution,
                 noise_level=c.sample.noise_level, mini_num_image_per_prompt=G, train_num_steps=T,
                 process_index=self.rank, sample_num_steps=c.sample.num_steps, random_timestep=c.sample.random_timestep,
-                seed=rollout_seed(c.seed, self.epoch * nb + i, self.rank), **sde_kw)        # TP:755-772
+                seed=rollout_seed(c.seed, self.epoch * nb + i, self.rank), **sde_kw, **mask_kw)        # TP:755-772
             first = int(self.pipe.last_random_timestep)
             score_prompts = prompts
             if hasattr(self.data, "prompt_text"):          # host scorers (ocr) read the strings, PickScore the ids
@@ -372,6 +386,8 @@ class Trainer:
                  "log_probs": torch.stack(lps, dim=1), "images": images, "clip_ids": prompts, "_future": fut}
             if ref is not None:
                 s["ref_images"] = ref
+            if pm is not None:
+                s["prompt_embeds_mask"] = pm
             return s, first
 
         self.pipe.cfg_two_streams = bool(c.sample.get("cfg_two_streams", False))     # the CFG halves of a forward on two HIP streams (same bits)
@@ -652,12 +668,15 @@ class Trainer:
                                                  "prompt_embeds", "pooled_prompt_embeds")}
                 embeds = torch.cat([neg_pe.repeat(G, 1, 1), s["prompt_embeds"]])            # TP:1084-1091
                 pooled = torch.cat([neg_ppe.repeat(G, 1), s["pooled_prompt_embeds"]])
+                embeds_mask = None
+                if "prompt_embeds_mask" in samples:                                         # same row order as `embeds`
+                    embeds_mask = torch.cat([self.data.neg_mask.to(self.device).repeat(G, 1), samples["prompt_embeds_mask"][sl]])
                 for j in range(T):
                     info = timed("micro_step", lambda: g_step.micro_step(
                         model, self.pipe.scheduler, s, j, embeds, pooled, s["log_probs"][:, j], s["advantages"][:, j],
                         guidance_scale=c.sample.guidance_scale, noise_level=c.sample.noise_level, adv_clip_max=c.train.adv_clip_max,
                         clip_range=c.train.clip_range, loss_scale=1.0 / (GA * T), step_index=samples["first_step_index"][i] + j,
-                        beta=c.train.beta, sde_type=c.sample.get("sde_type") or "cps"))
+                        beta=c.train.beta, sde_type=c.sample.get("sde_type") or "cps", embeds_mask=embeds_mask))
                     for k in ("loss", "approx_kl", "clipfrac", "clipfrac_gt_one", "clipfrac_lt_one", "policy_loss") + \
                             (("kl_loss",) if c.train.beta > 0 else ()):                     # TP:1158-1160
                         agg[k] = agg.get(k, 0) + info[k]

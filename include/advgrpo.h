@@ -26,7 +26,7 @@ extern "C" {
 
 #define ADVGRPO_ABI_VERSION 1
 
-enum advgrpo_dtype { ADVGRPO_F32 = 0, ADVGRPO_BF16 = 1, ADVGRPO_F64 = 2, ADVGRPO_U8 = 3 };
+enum advgrpo_dtype { ADVGRPO_F32 = 0, ADVGRPO_BF16 = 1, ADVGRPO_F64 = 2, ADVGRPO_U8 = 3, ADVGRPO_I32 = 4, ADVGRPO_I64 = 5 };
 
 int advgrpo_abi_version(void);
 const char* advgrpo_last_error(void);
@@ -322,6 +322,33 @@ int advgrpo_attention_bwd(const void* q, const void* k, const void* v, const voi
                           int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddq,
                           int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso, int64_t bsdo, int64_t bsdq,
                           int B, int H, int Sq, int Skv, int head_dim, float scale, void* stream);
+
+/* Per-sample lengths (the Qwen-Image MMDiT's encoder_hidden_states_mask; csrc/attention_varlen.hip).  Self-attention over rows laid out
+ * [image rows ; right-padded text rows]: q, k, v, o share one padded length S, and seq_lens (int32 [B] ON THE DEVICE, read by the kernels at
+ * run time: no host sync, and a captured graph follows later writes to it) gives the valid prefix of each sample.  Sample b is computed
+ * exactly as if it had been launched alone at Sq = Skv = seq_lens[b] -- bit for bit what advgrpo_attention_fwd / advgrpo_attention_bwd give
+ * for that sample at that length.  Head dim 128 only, non-causal, no bias; alignment as for those entries at head dim 128 (ld* % 8 == 0,
+ * 16-byte aligned o rows; backward: every pointer and pitch 16-byte aligned).
+ *   THE CLAMP: a length outside [1, S] is clamped into it by the kernels (0 or a negative value behaves as 1, S + 7 as S); nothing is counted.
+ *   THE ZERO ROWS: rows seq_lens[b] .. S - 1 of sample b are never read into a result (they may hold anything, NaN included), and where
+ *   they are outputs -- o, lse, dq, dk, dv -- they are written as zeros, so every element of every output is written.
+ * lse (optional in the forward, f32 [B, H, S]) and work (backward: B * H * S f32) keep the padded pitch S.  The running-maximum fallback and
+ * its counter (advgrpo_attention_fallback_count) are those of advgrpo_attention_fwd.  Every refusal comes before the first launch. */
+int advgrpo_attention_fwd_varlen(const void* q, const void* k, const void* v, void* o,
+                                 int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                                 int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso,
+                                 int B, int H, int S, int head_dim, float scale,
+                                 const int32_t* seq_lens, float* lse, void* stream);
+int advgrpo_attention_bwd_varlen(const void* q, const void* k, const void* v, const void* o, const void* d_o,
+                                 const float* lse, float* work, void* dq, void* dk, void* dv,
+                                 int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddq,
+                                 int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso, int64_t bsdo, int64_t bsdq,
+                                 int B, int H, int S, int head_dim, float scale, const int32_t* seq_lens, void* stream);
+/* mask [B, Nt] (contiguous; mask_dtype ADVGRPO_U8 for bool / uint8, ADVGRPO_I32 or ADVGRPO_I64) -> seq_lens[b] = base + the number of LEADING
+ * non-zero entries of row b (int32 on the device).  A row that is not a right-padded prefix -- a non-zero entry behind a zero, or no leading
+ * non-zero entry at all -- is counted once in bad (int32 on the device, may be NULL; the caller zeroes and reads it), in the manner of
+ * advgrpo_token_embed's bad_ids.  No device assert, no host sync. */
+int advgrpo_mask_to_seq_lens(const void* mask, int mask_dtype, int32_t* seq_lens, int B, int Nt, int base, int* bad, void* stream);
 
 /* ------------------------------------------------------------------ VAE decoder pieces
  * Replace diffusers AutoencoderKL.decode + VaeImageProcessor.postprocess("pt") as reached at
