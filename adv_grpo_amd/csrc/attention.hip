@@ -211,7 +211,6 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttnParams p) 
                     (__attribute__((address_space(3))) s16x4*)(a0));
                 const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
                     (__attribute__((address_space(3))) s16x4*)(a1));
-                typedef __attribute__((ext_vector_type(8))) short s16x8;
                 const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                 const bf16x8_t vf = __builtin_bit_cast(bf16x8_t, both);
 #pragma unroll
@@ -439,7 +438,6 @@ __global__ __launch_bounds__(RES_THREADS) void attention_fwd_resident_kernel(con
                         const bf16_t* a1 = a0 + 16 * VP;
                         const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
                         const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a1));
-                        typedef __attribute__((ext_vector_type(8))) short s16x8;
                         const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                         const bf16x8_t vf = __builtin_bit_cast(bf16x8_t, both);
 #pragma unroll
@@ -559,8 +557,8 @@ __global__ __launch_bounds__(256, ATT_WGS) void attention_fwd_glds_kernel(const 
                 ks = kp + (int64_t)r * p.ldk + k_src_chunk * 8;
                 vs = vp + (int64_t)r * p.ldv + v_chunk[i];
             }
-            att_dma16(ks, base + j * 1024);
-            att_dma16(vs, base + TILE_B + j * 1024);
+            lds_dma16_ptr(ks, base + j * 1024);
+            lds_dma16_ptr(vs, base + TILE_B + j * 1024);
             k_src[i] += k_step;
             v_src[i] += v_step;
         }
@@ -596,7 +594,7 @@ __global__ __launch_bounds__(256, ATT_WGS) void attention_fwd_glds_kernel(const 
     int slot = 0;
     for (int it = 0; it < nt; ++it) {
         const int kv0 = it * ATT_KB;
-        if (NS > 2 && it + 1 < nt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
+        if (NS > 2 && it + 1 < nt) wait_vm<LOADS>();
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         const int fill = slot == 0 ? NS - 1 : slot - 1;   // slot of tile it-1: free after this barrier
@@ -664,7 +662,6 @@ __global__ __launch_bounds__(256, ATT_WGS) void attention_fwd_glds_kernel(const 
             const float alpha = __builtin_amdgcn_exp2f(m_run[qb] - m_use);
             m_run[qb] = m_new;
             // exp2(s * scale - m) two scores per v_pk_fma_f32; row sums on v_pk_add_f32
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
             const f32x2 sc2 = {sc, sc}, nm2 = {-m_use, -m_use};
             f32x2 ps2 = {0.f, 0.f};
 #pragma unroll
@@ -704,7 +701,6 @@ __global__ __launch_bounds__(256, ATT_WGS) void attention_fwd_glds_kernel(const 
                 const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
                 const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
                     (__attribute__((address_space(3))) s16x4*)(a0 + 2048));
-                typedef __attribute__((ext_vector_type(8))) short s16x8;
                 const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                 const bf16x8_t vf = __builtin_bit_cast(bf16x8_t, both);
 #pragma unroll

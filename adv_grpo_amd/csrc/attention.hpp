@@ -1,4 +1,4 @@
-// attention.hpp -- parameter block and LDS-DMA / lane-swap helpers shared by the attention forward kernels.
+// attention.hpp -- parameter block and lane-swap helpers shared by the attention forward kernels.
 #pragma once
 #include "common.hpp"
 #include "gemm.hpp"
@@ -22,8 +22,6 @@ struct AttnVarlenParams : AttnParams {
     const int* seq_lens;
 };
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
 constexpr int ATT_QB = 128;   // queries per workgroup
 constexpr int ATT_KB = 64;    // keys per tile
 
@@ -38,14 +36,6 @@ __device__ __forceinline__ float xor16_max(float v) { float a = v, b = v; ADVGRP
 __device__ __forceinline__ float xor32_max(float v) { float a = v, b = v; ADVGRPO_SWAP32(a, b); return fmaxf(a, b); }
 __device__ __forceinline__ float xor16_add(float v) { float a = v, b = v; ADVGRPO_SWAP16(a, b); return a + b; }
 __device__ __forceinline__ float xor32_add(float v) { float a = v, b = v; ADVGRPO_SWAP32(a, b); return a + b; }
-
-// One LDS-DMA instruction (64 lanes x 16 bytes -> LDS [lds, lds + 1 KiB)), hand-written: issued through the builtin the
-// compiler treats the DMA as a possible alias of every later ds_read and puts s_waitcnt vmcnt(0) in front of the first
-// fragment read of the SAME iteration.  Ring hazards are covered by the caller's counted wait + barrier.
-__device__ __forceinline__ void att_dma16(const void* src, const char* lds) {
-    const uint32_t l = (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)(lds));
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(l) : "memory");
-}
 
 // the software-pipelined head-dim-64 forward (attention_pipe.hip): non-causal, no score bias, 16-byte aligned output rows
 int attention_fwd_pipe_launch(const AttnParams& p, hipStream_t s);

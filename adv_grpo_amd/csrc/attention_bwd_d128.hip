@@ -24,8 +24,6 @@ namespace advgrpo {
 
 namespace {
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 // B8_CB (template): 16-row blocks of own rows per wave -- every A fragment read from LDS feeds B8_CB MFMAs; a workgroup owns 64 B8_CB rows
 constexpr int B8_ROWS = 32;           // streamed rows per tile
 constexpr int B8_HD = 128;
@@ -34,11 +32,6 @@ constexpr int B8_RP = B8_HD;          // row-major tile pitch (elements): 256 by
 constexpr int B8_TP = B8_ROWS + 4;    // transposed tile pitch (elements): 72 bytes -- the eight d-rows one wave's transposing
                                       // stores hit are 576 bytes apart: four bank groups (80 bytes put them on two)
 constexpr int B8_ROWMAJ = B8_ROWS * B8_RP * 2, B8_TRANS = B8_HD * B8_TP * 2;      // bytes
-
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2v_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack2(f32x2_t v) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2v_t)); }   // v_cvt_pk_bf16_f32
-__device__ __forceinline__ uint32_t b8_pack(float lo, float hi) { return pack2(f32x2_t{lo, hi}); }
 
 // per-sample length of the VARLEN bodies: seq_lens[b] clamped into [1, S], wave-uniform
 __device__ __forceinline__ int b8_len(const int* __restrict__ seq_lens, int b, int S) {
@@ -111,11 +104,11 @@ __global__ __launch_bounds__(256, B8_CB == 1 ? (DKDV ? 3 : 4) : 2) void attn_bwd
         if constexpr (!DKDV) { negL_own[cb] = -Lp[own_r]; negD_own[cb] = -Dp[own_r]; }
     }
 
-    f32x4_t acc0[B8_CB][8], acc1[B8_CB][8];
+    f32x4 acc0[B8_CB][8], acc1[B8_CB][8];
 #pragma unroll
     for (int cb = 0; cb < B8_CB; ++cb)
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { acc0[cb][i] = f32x4_t{0.f, 0.f, 0.f, 0.f}; acc1[cb][i] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
+        for (int i = 0; i < 8; ++i) { acc0[cb][i] = f32x4{0.f, 0.f, 0.f, 0.f}; acc1[cb][i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
     // tile loader: thread -> (row = tid >> 3, 16-byte chunks (tid & 7) and (tid & 7) + 8) of both operands
     const int lrow = tid >> 3, lch = tid & 7;
@@ -178,7 +171,7 @@ __global__ __launch_bounds__(256, B8_CB == 1 ? (DKDV ? 3 : 4) : 2) void attn_bwd
     };
 
     const int nt = (n_str + B8_ROWS - 1) / B8_ROWS;
-    f32x4_t zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     asm volatile("" : "+v"(zero4));            // (opaque: stays ONE register quad instead of being re-materialised per use)
     fetch(0);
     for (int t = 0; t < nt; ++t) {
@@ -189,7 +182,7 @@ __global__ __launch_bounds__(256, B8_CB == 1 ? (DKDV ? 3 : 4) : 2) void attn_bwd
 
         const bool last_ragged = t == nt - 1 && nt * B8_ROWS > n_str;       // (uniform: only the last tile of a ragged sequence masks keys)
         // ---- scores and dP of the two 16-row blocks of the tile x the wave's B8_CB own-row blocks
-        f32x4_t sc[2][B8_CB], dp[2][B8_CB];
+        f32x4 sc[2][B8_CB], dp[2][B8_CB];
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) {
 #pragma unroll
@@ -222,8 +215,8 @@ __global__ __launch_bounds__(256, B8_CB == 1 ? (DKDV ? 3 : 4) : 2) void attn_bwd
                     ds[rb * 4 + r] = pe * (dp[rb][cb][r] + nd);
                 }
             uint4 dsw, pw;
-            dsw.x = b8_pack(ds[0], ds[1]); dsw.y = b8_pack(ds[2], ds[3]); dsw.z = b8_pack(ds[4], ds[5]); dsw.w = b8_pack(ds[6], ds[7]);
-            pw.x = b8_pack(pv[0], pv[1]); pw.y = b8_pack(pv[2], pv[3]); pw.z = b8_pack(pv[4], pv[5]); pw.w = b8_pack(pv[6], pv[7]);
+            dsw.x = cvt_pk_bf16(ds[0], ds[1]); dsw.y = cvt_pk_bf16(ds[2], ds[3]); dsw.z = cvt_pk_bf16(ds[4], ds[5]); dsw.w = cvt_pk_bf16(ds[6], ds[7]);
+            pw.x = cvt_pk_bf16(pv[0], pv[1]); pw.y = cvt_pk_bf16(pv[2], pv[3]); pw.z = cvt_pk_bf16(pv[4], pv[5]); pw.w = cvt_pk_bf16(pv[6], pv[7]);
             dsf[cb] = __builtin_bit_cast(bf16x8_t, dsw);
             pf[cb] = __builtin_bit_cast(bf16x8_t, pw);
         }
@@ -280,8 +273,8 @@ __global__ __launch_bounds__(256, B8_CB == 1 ? (DKDV ? 3 : 4) : 2) void attn_bwd
 #pragma unroll
         for (int db = 0; db < 8; ++db) {
             uint2 v;
-            v.x = b8_pack(acc0[cb][db][0] * p.scale, acc0[cb][db][1] * p.scale);
-            v.y = b8_pack(acc0[cb][db][2] * p.scale, acc0[cb][db][3] * p.scale);
+            v.x = cvt_pk_bf16(acc0[cb][db][0] * p.scale, acc0[cb][db][1] * p.scale);
+            v.y = cvt_pk_bf16(acc0[cb][db][2] * p.scale, acc0[cb][db][3] * p.scale);
             if constexpr (VARLEN) { if (pad) v = uint2{0u, 0u}; }
             *reinterpret_cast<uint2*>(o0 + db * 16 + kg * 4) = v;
         }
@@ -290,8 +283,8 @@ __global__ __launch_bounds__(256, B8_CB == 1 ? (DKDV ? 3 : 4) : 2) void attn_bwd
 #pragma unroll
             for (int db = 0; db < 8; ++db) {
                 uint2 v;
-                v.x = b8_pack(acc1[cb][db][0], acc1[cb][db][1]);
-                v.y = b8_pack(acc1[cb][db][2], acc1[cb][db][3]);
+                v.x = cvt_pk_bf16(acc1[cb][db][0], acc1[cb][db][1]);
+                v.y = cvt_pk_bf16(acc1[cb][db][2], acc1[cb][db][3]);
                 if constexpr (VARLEN) { if (pad) v = uint2{0u, 0u}; }
                 *reinterpret_cast<uint2*>(o1 + db * 16 + kg * 4) = v;
             }
@@ -306,7 +299,6 @@ __global__ __launch_bounds__(256, B8_CB == 1 ? (DKDV ? 3 : 4) : 2) void attn_bwd
 // C layout "column = own key (lane & 31), rows = queries 8 (r >> 2) + 4 (lane >> 5) + (r & 3)", which is the B operand of the
 // accumulating products when k-slot j of k-step s and group g = lane >> 5 stands for query 16 s + 8 (j >> 2) + 4 g + (j & 3) = C
 // register 8 s + j; the A operand (the transposed tile) is read with that permutation as two 8-byte reads 8 queries apart.
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
 template <bool DKDV, int AHEAD = 0, bool LATE = false, bool VARLEN = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const b8_params<VARLEN> p) {
@@ -372,7 +364,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const b8_para
             negD_own = -Dp[own_r];
         }
     }
-    f32x16_t acc0[4], acc1[DKDV ? 4 : 1];
+    f32x16 acc0[4], acc1[DKDV ? 4 : 1];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -452,7 +444,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const b8_para
         const char* x0c = reinterpret_cast<const char*>(x0);
         const char* xvc = reinterpret_cast<const char*>(xv) + (wave * 32) * (B8_RP * 2);
         // ---- scores and dP: the tile's 32 rows x the wave's 32 own rows, k = d in 8 steps of 16
-        f32x16_t sc, dp;
+        f32x16 sc, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { sc[r] = 0.f; dp[r] = 0.f; }
         if constexpr (AHEAD > 0) {
@@ -500,10 +492,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const b8_para
             uint32_t pw[4], dw[4];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {                       // C registers 8 s + 4 u .. + 3 = streamed rows 16 s + 8 u + 4 hi + 0..3
-                f32x4_t nl, nd;
+                f32x4 nl, nd;
                 if constexpr (DKDV) {
-                    nl = *reinterpret_cast<const f32x4_t*>(lvec + 16 * s + 8 * u + 4 * hi);
-                    nd = *reinterpret_cast<const f32x4_t*>(dvec + 16 * s + 8 * u + 4 * hi);
+                    nl = *reinterpret_cast<const f32x4*>(lvec + 16 * s + 8 * u + 4 * hi);
+                    nd = *reinterpret_cast<const f32x4*>(dvec + 16 * s + 8 * u + 4 * hi);
                 } else {
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
@@ -514,14 +506,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const b8_para
 #pragma unroll
                 for (int v = 0; v < 2; ++v) {
                     const int r = 8 * s + 4 * u + 2 * v;
-                    f32x2_t pe, dd;
+                    f32x2 pe, dd;
                     pe.x = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[r], c, nl[2 * v]));
                     pe.y = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[r + 1], c, nl[2 * v + 1]));
                     dd.x = dp[r] + nd[2 * v];
                     dd.y = dp[r + 1] + nd[2 * v + 1];
                     dd = dd * pe;
-                    if constexpr (DKDV) pw[2 * u + v] = pack2(pe);
-                    dw[2 * u + v] = pack2(dd);
+                    if constexpr (DKDV) pw[2 * u + v] = cvt_pk_bf16(pe);
+                    dw[2 * u + v] = cvt_pk_bf16(dd);
                 }
             }
             uint4 dsw, pww;
@@ -591,8 +583,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const b8_para
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 uint2 v;
-                v.x = pack2(f32x2_t{acc0[db][4 * q] * p.scale, acc0[db][4 * q + 1] * p.scale});
-                v.y = pack2(f32x2_t{acc0[db][4 * q + 2] * p.scale, acc0[db][4 * q + 3] * p.scale});
+                v.x = cvt_pk_bf16(f32x2{acc0[db][4 * q] * p.scale, acc0[db][4 * q + 1] * p.scale});
+                v.y = cvt_pk_bf16(f32x2{acc0[db][4 * q + 2] * p.scale, acc0[db][4 * q + 3] * p.scale});
                 if constexpr (VARLEN) { if (pad) v = uint2{0u, 0u}; }
                 *reinterpret_cast<uint2*>(o0 + db * 32 + 8 * q + 4 * hi) = v;
             }
@@ -603,8 +595,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_d128_w32_kernel(const b8_para
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     uint2 w;
-                    w.x = pack2(f32x2_t{acc1[db][4 * q], acc1[db][4 * q + 1]});
-                    w.y = pack2(f32x2_t{acc1[db][4 * q + 2], acc1[db][4 * q + 3]});
+                    w.x = cvt_pk_bf16(f32x2{acc1[db][4 * q], acc1[db][4 * q + 1]});
+                    w.y = cvt_pk_bf16(f32x2{acc1[db][4 * q + 2], acc1[db][4 * q + 3]});
                     if constexpr (VARLEN) { if (pad) w = uint2{0u, 0u}; }
                     *reinterpret_cast<uint2*>(o1 + db * 32 + 8 * q + 4 * hi) = w;
                 }

@@ -60,10 +60,6 @@ namespace advgrpo {
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-
 constexpr int BP_ROWS = 32;                 // streamed rows per tile
 constexpr int BP_TILE = BP_ROWS * 128;      // bytes
 constexpr int BP_RING = 8;                  // tiles per ring
@@ -72,33 +68,10 @@ constexpr int BP_VEC = 2 * BP_RING1;        // byte offset of the (-L/c | -D) ve
 constexpr int BP_LDS_DQ = BP_VEC, BP_LDS_DKDV = BP_VEC + BP_RING * 256;
 constexpr int BP_OWN = BP_WAVES * 32;      // own rows per workgroup
 
-#define BP_SB() __builtin_amdgcn_sched_barrier(0)
-#define BP_PIN(x) asm volatile("" : "+v"(x))
-#define BP_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-
-__device__ __forceinline__ uint32_t bp_cvt_pk(float lo, float hi) {      // (through the compiler: see attention_pipe.hip)
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    const f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
 __device__ __forceinline__ float bp_exp2(float x) {
     if constexpr ((BP_ABL & 2) != 0) return x * 0.75f;
     return __builtin_amdgcn_exp2f(x);
 }
-template <int N>
-__device__ __forceinline__ void bp_wait_vm() {
-    static_assert(N == 0 || N == 1 || N == 2 || N == 3 || N == 4 || N == 6 || N == 9, "add the literal");
-    if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-}
-template <int N>
-using int_c = std::integral_constant<int, N>;
 
 // The VALU work of one tile as a list of single instructions in issue order, dealt evenly over the MFMA slots of a step:
 // element k (0..15) of the lane's 16 scores: X scale (0), E exponential (1), M multiply by dP - D (2); pair i: C pack dS (3),
@@ -123,10 +96,6 @@ constexpr BpSched<DKDV> bp_make_sched() {
 }
 template <bool DKDV>
 inline constexpr BpSched<DKDV> bp_sched = bp_make_sched<DKDV>();
-template <int N0, class F, int... I>
-__device__ __forceinline__ void bp_for(F&& f, std::integer_sequence<int, I...>) {
-    (f(int_c<N0 + I>{}), ...);
-}
 
 template <bool DKDV>
 __global__ __launch_bounds__(BP_WAVES * 64, BP_WAVES == 4 ? 2 : 1) void attn_bwd_pipe_kernel(const AttnBwdParams p) {
@@ -180,12 +149,12 @@ __global__ __launch_bounds__(BP_WAVES * 64, BP_WAVES == 4 ? 2 : 1) void attn_bwd
     const int R = (wave & 3) * 8 + (lane >> 3), pch = lane & 7;
     const uint32_t sw = (uint32_t)((pch ^ ((((R >> 1) & 1) << 2) | ((R >> 2) & 3))) << 4);      // source chunk of LDS chunk pch
     const uint32_t x0_lo = (uint32_t)R * ld0b + sw, x1_lo = (uint32_t)R * ld1b + sw;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)(smem)) + (wave & 3) * 1024;
-    const uint32_t ldsv = (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)(smem)) + BP_VEC;
+    const uint32_t lds0 = lds_addr(smem) + (wave & 3) * 1024;
+    const uint32_t ldsv = lds_addr(smem) + BP_VEC;
     const uint32_t lane4 = lane * 4;
     auto dma16 = [&](const char* base, uint32_t off, uint32_t lds) __attribute__((always_inline)) {
         if constexpr ((BP_ABL & 8) != 0) return;
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(lds) : "memory");
+        lds_dma16(base, off, lds);
     };
     auto dma4 = [&](const char* base, uint32_t off, uint32_t lds) __attribute__((always_inline)) {
         if constexpr ((BP_ABL & 8) != 0) return;
@@ -280,7 +249,7 @@ __global__ __launch_bounds__(BP_WAVES * 64, BP_WAVES == 4 ? 2 : 1) void attn_bwd
     if (nt > 1) stage(1, 1);
     if (nt > 2) stage(2, 2);
     if (nt > 3) stage(3, 3);
-    bp_wait_vm<0>();
+    wait_vm<0>();
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) { asm volatile("" ::"v"(bf0[ks])); asm volatile("" ::"v"(bf1[ks])); }
     asm volatile("" ::"v"(nl), "v"(negD16));
@@ -289,8 +258,8 @@ __global__ __launch_bounds__(BP_WAVES * 64, BP_WAVES == 4 ? 2 : 1) void attn_bwd
     else { sc[0] = zero16; dp[0] = negD16; }
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-        sc[0] = BP_MFMA(rfrag(0, ks), bf0[ks], sc[0]);
-        dp[0] = BP_MFMA(rfrag(BP_RING1, ks), bf1[ks], dp[0]);
+        sc[0] = ADVGRPO_MFMA32(rfrag(0, ks), bf0[ks], sc[0]);
+        dp[0] = ADVGRPO_MFMA32(rfrag(BP_RING1, ks), bf1[ks], dp[0]);
     }
 
     // ---- one step: g = SL (mod 8); VALU on tile g (score set SL & 1), accumulating products of tile g - 1, scores of tile g + 1
@@ -302,9 +271,9 @@ __global__ __launch_bounds__(BP_WAVES * 64, BP_WAVES == 4 ? 2 : 1) void attn_bwd
         constexpr int V_NEXT = ((SL + 1) & 7) * 256;
         if constexpr ((BP_ABL & 1) == 0) {
             // needed now: tile g + 1 (requested in step g - 3); still in flight: tiles g + 2, g + 3
-            if (g + 3 < nt) bp_wait_vm<2 * NB>();
-            else if (g + 2 < nt) bp_wait_vm<NB>();
-            else bp_wait_vm<0>();
+            if (g + 3 < nt) wait_vm<2 * NB>();
+            else if (g + 2 < nt) wait_vm<NB>();
+            else wait_vm<0>();
             __builtin_amdgcn_s_barrier();
         }
         if constexpr (BP_DMA_SLOT < 0) {
@@ -341,38 +310,38 @@ __global__ __launch_bounds__(BP_WAVES * 64, BP_WAVES == 4 ? 2 : 1) void attn_bwd
             if constexpr (op.kind == 0) {
                 if constexpr (DKDV) xv[k] = sc[CUR][k] * c;
                 else xv[k] = __builtin_fmaf(sc[CUR][k], c, nl);
-                BP_PIN(xv[k]);
+                ADVGRPO_PIN(xv[k]);
             } else if constexpr (op.kind == 1) {
                 ev[k] = bp_exp2(xv[k]);
-                BP_PIN(ev[k]);
+                ADVGRPO_PIN(ev[k]);
             } else if constexpr (op.kind == 2) {
                 xv[k] = ev[k] * dp[CUR][k];
-                BP_PIN(xv[k]);
+                ADVGRPO_PIN(xv[k]);
             } else if constexpr (op.kind == 3) {
-                dsf[CUR][k >> 2][k & 3] = bp_cvt_pk(xv[2 * k], xv[2 * k + 1]);
-                BP_PIN(dsf[CUR][k >> 2][k & 3]);
+                dsf[CUR][k >> 2][k & 3] = cvt_pk_bf16(xv[2 * k], xv[2 * k + 1]);
+                ADVGRPO_PIN(dsf[CUR][k >> 2][k & 3]);
             } else {
-                pf[CUR][k >> 2][k & 3] = bp_cvt_pk(ev[2 * k], ev[2 * k + 1]);
-                BP_PIN(pf[CUR][k >> 2][k & 3]);
+                pf[CUR][k >> 2][k & 3] = cvt_pk_bf16(ev[2 * k], ev[2 * k + 1]);
+                ADVGRPO_PIN(pf[CUR][k >> 2][k & 3]);
             }
         };
         auto slot = [&](auto s_tag) __attribute__((always_inline)) {
             constexpr int s = decltype(s_tag)::value;
-            BP_SB();
+            ADVGRPO_SB();
             if constexpr (s < NA) {
                 if constexpr (!FIRST) {
                     constexpr int kk = (s & 3) >> 1, db = s & 1;
-                    if constexpr (DKDV && s < 4) acc1[db] = BP_MFMA(a[s & 3], __builtin_bit_cast(bf16x8_t, pf[NXT][kk]), acc1[db]);
-                    else acc0[db] = BP_MFMA(a[s & 3], __builtin_bit_cast(bf16x8_t, dsf[NXT][kk]), acc0[db]);
+                    if constexpr (DKDV && s < 4) acc1[db] = ADVGRPO_MFMA32(a[s & 3], __builtin_bit_cast(bf16x8_t, pf[NXT][kk]), acc1[db]);
+                    else acc0[db] = ADVGRPO_MFMA32(a[s & 3], __builtin_bit_cast(bf16x8_t, dsf[NXT][kk]), acc0[db]);
                 }
             } else if constexpr (s < NS && !LAST) {
                 constexpr int ks = (s - NA) >> 1, which = (s - NA) & 1;
                 if constexpr (which == 0) {
-                    if constexpr (ks == 0 && !DKDV) sc[NXT] = BP_MFMA(a[s & 3], bf0[0], zero16);
-                    else sc[NXT] = BP_MFMA(a[s & 3], bf0[ks], sc[NXT]);
+                    if constexpr (ks == 0 && !DKDV) sc[NXT] = ADVGRPO_MFMA32(a[s & 3], bf0[0], zero16);
+                    else sc[NXT] = ADVGRPO_MFMA32(a[s & 3], bf0[ks], sc[NXT]);
                 } else {
-                    if constexpr (ks == 0 && !DKDV) dp[NXT] = BP_MFMA(a[s & 3], bf1[0], negD16);
-                    else dp[NXT] = BP_MFMA(a[s & 3], bf1[ks], dp[NXT]);
+                    if constexpr (ks == 0 && !DKDV) dp[NXT] = ADVGRPO_MFMA32(a[s & 3], bf1[0], negD16);
+                    else dp[NXT] = ADVGRPO_MFMA32(a[s & 3], bf1[ks], dp[NXT]);
                 }
             }
             if constexpr (s < NS && needs_operand(s + BP_AHEAD)) a[(s + BP_AHEAD) & 3] = operand(int_c<s + BP_AHEAD>{});
@@ -386,37 +355,35 @@ __global__ __launch_bounds__(BP_WAVES * 64, BP_WAVES == 4 ? 2 : 1) void attn_bwd
             // this slot's share of the VALU list (the empty asm statements keep each instruction in its slot, see attention_pipe.hip)
             if constexpr (s >= VS0) {
                 constexpr int n0 = (s - VS0) * NOPS / (NS - VS0), n1 = (s - VS0 + 1) * NOPS / (NS - VS0);
-                bp_for<n0>(valu, std::make_integer_sequence<int, n1 - n0>{});
+                static_for_range<n0, n1>(valu);
             }
         };
         slot(int_c<0>{}); slot(int_c<1>{}); slot(int_c<2>{}); slot(int_c<3>{});
         slot(int_c<4>{}); slot(int_c<5>{}); slot(int_c<6>{}); slot(int_c<7>{});
         slot(int_c<8>{}); slot(int_c<9>{}); slot(int_c<10>{}); slot(int_c<11>{});
         if constexpr (NS > 12) { slot(int_c<12>{}); slot(int_c<13>{}); slot(int_c<14>{}); slot(int_c<15>{}); }
-        BP_SB();
+        ADVGRPO_SB();
     };
 
-    typedef std::integral_constant<bool, true> yes_t;
-    typedef std::integral_constant<bool, false> no_t;
     // (a LAST instantiation of the step without the score products of a tile that does not exist costs registers on every path:
     // 246 / 256 VGPRs + 344 bytes of scratch with the eight extra copies, measured 13 % slower; the last step multiplies a stale
     // ring slot instead and nobody reads the result)
-    step(int_c<0>{}, yes_t{}, no_t{}, 0);
+    step(int_c<0>{}, true_c{}, false_c{}, 0);
     int g = 1;
     for (; g + 8 <= nt; g += 8) {
-        step(int_c<1>{}, no_t{}, no_t{}, g);     step(int_c<2>{}, no_t{}, no_t{}, g + 1);
-        step(int_c<3>{}, no_t{}, no_t{}, g + 2); step(int_c<4>{}, no_t{}, no_t{}, g + 3);
-        step(int_c<5>{}, no_t{}, no_t{}, g + 4); step(int_c<6>{}, no_t{}, no_t{}, g + 5);
-        step(int_c<7>{}, no_t{}, no_t{}, g + 6); step(int_c<0>{}, no_t{}, no_t{}, g + 7);
+        step(int_c<1>{}, false_c{}, false_c{}, g);     step(int_c<2>{}, false_c{}, false_c{}, g + 1);
+        step(int_c<3>{}, false_c{}, false_c{}, g + 2); step(int_c<4>{}, false_c{}, false_c{}, g + 3);
+        step(int_c<5>{}, false_c{}, false_c{}, g + 4); step(int_c<6>{}, false_c{}, false_c{}, g + 5);
+        step(int_c<7>{}, false_c{}, false_c{}, g + 6); step(int_c<0>{}, false_c{}, false_c{}, g + 7);
     }
     // (g = 1 (mod 8) here) the up to seven left-over steps
-    if (g < nt) { step(int_c<1>{}, no_t{}, no_t{}, g); ++g; }
-    if (g < nt) { step(int_c<2>{}, no_t{}, no_t{}, g); ++g; }
-    if (g < nt) { step(int_c<3>{}, no_t{}, no_t{}, g); ++g; }
-    if (g < nt) { step(int_c<4>{}, no_t{}, no_t{}, g); ++g; }
-    if (g < nt) { step(int_c<5>{}, no_t{}, no_t{}, g); ++g; }
-    if (g < nt) { step(int_c<6>{}, no_t{}, no_t{}, g); ++g; }
-    if (g < nt) { step(int_c<7>{}, no_t{}, no_t{}, g); ++g; }
+    if (g < nt) { step(int_c<1>{}, false_c{}, false_c{}, g); ++g; }
+    if (g < nt) { step(int_c<2>{}, false_c{}, false_c{}, g); ++g; }
+    if (g < nt) { step(int_c<3>{}, false_c{}, false_c{}, g); ++g; }
+    if (g < nt) { step(int_c<4>{}, false_c{}, false_c{}, g); ++g; }
+    if (g < nt) { step(int_c<5>{}, false_c{}, false_c{}, g); ++g; }
+    if (g < nt) { step(int_c<6>{}, false_c{}, false_c{}, g); ++g; }
+    if (g < nt) { step(int_c<7>{}, false_c{}, false_c{}, g); ++g; }
 
     // ---- the accumulating products of the last tile
     {
@@ -426,9 +393,9 @@ __global__ __launch_bounds__(BP_WAVES * 64, BP_WAVES == 4 ? 2 : 1) void attn_bwd
             for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    acc0[db] = BP_MFMA(tfrag(toff + kk * 2048, db), __builtin_bit_cast(bf16x8_t, ds_[kk]), acc0[db]);
+                    acc0[db] = ADVGRPO_MFMA32(tfrag(toff + kk * 2048, db), __builtin_bit_cast(bf16x8_t, ds_[kk]), acc0[db]);
                     if constexpr (DKDV)
-                        acc1[db] = BP_MFMA(tfrag(BP_RING1 + toff + kk * 2048, db), __builtin_bit_cast(bf16x8_t, p_[kk]), acc1[db]);
+                        acc1[db] = ADVGRPO_MFMA32(tfrag(BP_RING1 + toff + kk * 2048, db), __builtin_bit_cast(bf16x8_t, p_[kk]), acc1[db]);
                 }
         };
         if ((nt - 1) & 1) last(dsf[1], pf[1]);
@@ -444,8 +411,8 @@ __global__ __launch_bounds__(BP_WAVES * 64, BP_WAVES == 4 ? 2 : 1) void attn_bwd
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 uint2 pk;
-                pk.x = bp_cvt_pk(acc[db][4 * i] * scl, acc[db][4 * i + 1] * scl);
-                pk.y = bp_cvt_pk(acc[db][4 * i + 2] * scl, acc[db][4 * i + 3] * scl);
+                pk.x = cvt_pk_bf16(acc[db][4 * i] * scl, acc[db][4 * i + 1] * scl);
+                pk.y = cvt_pk_bf16(acc[db][4 * i + 2] * scl, acc[db][4 * i + 3] * scl);
                 *reinterpret_cast<uint2*>(ob + ql * 128 + (((db * 4 + i) ^ (ql & 7)) << 4) + hi * 8) = pk;
             }
         // (each wave reads back only what it wrote itself: no barrier, the LDS accesses of one wave are ordered)

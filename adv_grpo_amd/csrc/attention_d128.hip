@@ -32,7 +32,6 @@
 //     group cover all sixteen 16-byte slots; V 64-byte quarter q of row r at q ^ (r & 3) -- the 4 key rows of a
 //     transposed read land on the four quarters of the bank row (PMC: 0.8 % bank-conflict cycles).
 #include "attention.hpp"
-#include "gemm_device.hpp"
 
 // timing experiments (scripts/ablate_d128.sh builds one library per value; the product build has 0): 1 = wave groups one half
 // apart (a barrier per half), 2 = s_setprio 1 around the K Q^T half, 4 = static priority for the second wave group,
@@ -51,9 +50,6 @@ __device__ unsigned long long g_d128_fallbacks = 0;     // workgroups that took 
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
 constexpr int D128_QB = 256;                  // queries per workgroup
 constexpr int D128_TILE = ATT_KB * 256;       // 16 KiB per K or V tile
 constexpr int D128_SLOTS = 4;
@@ -61,25 +57,14 @@ constexpr int D128_VRING = D128_SLOTS * D128_TILE;          // byte offset of th
 constexpr int D128_LDS = 2 * D128_SLOTS * D128_TILE + 64;   // 128 KiB + the fallback flags
 constexpr bool D128_STAGGER = (D128_VAR & 1) != 0;
 
-__device__ __forceinline__ float d128_max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-// (through the compiler, not inline asm: see attention_pipe.hip -- the hazard recogniser only pads instructions it knows)
-__device__ __forceinline__ uint32_t d128_cvt_pk(float lo, float hi) {
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    const f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
+// experiment D128_VAR & 8: no slot pins
 #if (D128_VAR & 8)
 #define D128_SB()
 #define D128_PIN(x)
 #else
-#define D128_SB() __builtin_amdgcn_sched_barrier(0)
-#define D128_PIN(x) asm volatile("" : "+v"(x))
+#define D128_SB() ADVGRPO_SB()
+#define D128_PIN(x) ADVGRPO_PIN(x)
 #endif
-#define D128_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-
-template <int N>
-using d128_int = std::integral_constant<int, N>;
 
 }  // namespace
 
@@ -149,10 +134,10 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
         }
     }
     const int64_t k_step = (int64_t)ATT_KB * p.ldk * 2, v_step = (int64_t)ATT_KB * p.ldv * 2;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)(smem)) + wave * 1024;
+    const uint32_t lds0 = lds_addr(smem) + wave * 1024;
     auto dma = [&](const char* base, uint32_t off, uint32_t lds) __attribute__((always_inline)) {
         if constexpr ((D128_VAR & 16) != 0) return;
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(lds) : "memory");
+        lds_dma16(base, off, lds);
     };
     // piece i (0, 1) of K tile t into ring slot `slot` / of V tile t into its own slot; slot: compile-time
     auto dma_k = [&](int t, auto slot_tag, auto i_tag) __attribute__((always_inline)) {
@@ -170,12 +155,12 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
     // piece = 0..3: K piece 0, K piece 1, V piece 0, V piece 1
     auto bundle_piece = [&](int t, auto t4_tag, auto piece_tag) __attribute__((always_inline)) {
         constexpr int T4 = decltype(t4_tag)::value & 3, piece = decltype(piece_tag)::value;
-        if constexpr (piece < 2) dma_k(min(t + 1, nt - 1), d128_int<T4 + 1>{}, d128_int<piece>{});
-        else dma_v(t, d128_int<T4>{}, d128_int<piece - 2>{});
+        if constexpr (piece < 2) dma_k(min(t + 1, nt - 1), int_c<T4 + 1>{}, int_c<piece>{});
+        else dma_v(t, int_c<T4>{}, int_c<piece - 2>{});
     };
     auto bundle = [&](int t, auto t4_tag) __attribute__((always_inline)) {
-        bundle_piece(t, t4_tag, d128_int<0>{}); bundle_piece(t, t4_tag, d128_int<1>{});
-        bundle_piece(t, t4_tag, d128_int<2>{}); bundle_piece(t, t4_tag, d128_int<3>{});
+        bundle_piece(t, t4_tag, int_c<0>{}); bundle_piece(t, t4_tag, int_c<1>{});
+        bundle_piece(t, t4_tag, int_c<2>{}); bundle_piece(t, t4_tag, int_c<3>{});
     };
 
     // ---- fragment read bases (bytes inside a tile; the ring slot and the block inside the tile are immediates)
@@ -191,7 +176,6 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
     for (int db = 0; db < 4; ++db)      // (the V ring's base is part of the per-lane offset: the immediates then stay below the 64 KiB of a DS offset field)
         v_off[db] = D128_VRING + vrow * 256 + ((db ^ (vrow & 3)) << 6) + ((lane >> 4) & 1) * 32 + (lane & 3) * 8;
 
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
     auto kfrag = [&](int imm, int ks) __attribute__((always_inline)) {          // imm = slot * TILE + kb * 8192
         if constexpr ((D128_VAR & 32) != 0) return qf[ks];
         return *reinterpret_cast<const bf16x8_t*>(smem + k_off[ks] + imm);
@@ -219,10 +203,10 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
     for (int ks = 0; ks < 8; ++ks) asm volatile("" ::"v"(qf[ks]));
 
     // ---- prologue: K(0) | bundle 0 = {K(1), V(0)} | bundle 1 = {K(2), V(1)} ; S(0) = K(0) Q^T ; reference maximum
-    dma_k(0, d128_int<0>{}, d128_int<0>{});
-    dma_k(0, d128_int<0>{}, d128_int<1>{});
-    bundle(0, d128_int<0>{});
-    if (nt > 1) bundle(1, d128_int<1>{});
+    dma_k(0, int_c<0>{}, int_c<0>{});
+    dma_k(0, int_c<0>{}, int_c<1>{});
+    bundle(0, int_c<0>{});
+    if (nt > 1) bundle(1, int_c<1>{});
     if (nt > 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -231,26 +215,26 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb) s[kb] = D128_MFMA(kfrag(kb * 8192, ks), qf[ks], ks == 0 ? zero16 : s[kb]);
+        for (int kb = 0; kb < 2; ++kb) s[kb] = ADVGRPO_MFMA32(kfrag(kb * 8192, ks), qf[ks], ks == 0 ? zero16 : s[kb]);
     auto row_max = [&](const f32x16 (&sc)[2]) __attribute__((always_inline)) {
-        float m0 = d128_max3(sc[0][0], sc[0][1], sc[0][2]);
-        float m1 = d128_max3(sc[0][3], sc[0][4], sc[0][5]);
-        float m2 = d128_max3(sc[1][0], sc[1][1], sc[1][2]);
-        float m3 = d128_max3(sc[1][3], sc[1][4], sc[1][5]);
-        m0 = d128_max3(m0, sc[0][6], sc[0][7]);
-        m1 = d128_max3(m1, sc[0][8], sc[0][9]);
-        m2 = d128_max3(m2, sc[1][6], sc[1][7]);
-        m3 = d128_max3(m3, sc[1][8], sc[1][9]);
-        m0 = d128_max3(m0, sc[0][10], sc[0][11]);
-        m1 = d128_max3(m1, sc[0][12], sc[0][13]);
-        m2 = d128_max3(m2, sc[1][10], sc[1][11]);
-        m3 = d128_max3(m3, sc[1][12], sc[1][13]);
-        m0 = d128_max3(m0, sc[0][14], sc[0][15]);
-        m2 = d128_max3(m2, sc[1][14], sc[1][15]);
-        m0 = d128_max3(m0, m1, m2);
-        float a = d128_max3(m0, m3, m3), bb = a;
+        float m0 = max3(sc[0][0], sc[0][1], sc[0][2]);
+        float m1 = max3(sc[0][3], sc[0][4], sc[0][5]);
+        float m2 = max3(sc[1][0], sc[1][1], sc[1][2]);
+        float m3 = max3(sc[1][3], sc[1][4], sc[1][5]);
+        m0 = max3(m0, sc[0][6], sc[0][7]);
+        m1 = max3(m1, sc[0][8], sc[0][9]);
+        m2 = max3(m2, sc[1][6], sc[1][7]);
+        m3 = max3(m3, sc[1][8], sc[1][9]);
+        m0 = max3(m0, sc[0][10], sc[0][11]);
+        m1 = max3(m1, sc[0][12], sc[0][13]);
+        m2 = max3(m2, sc[1][10], sc[1][11]);
+        m3 = max3(m3, sc[1][12], sc[1][13]);
+        m0 = max3(m0, sc[0][14], sc[0][15]);
+        m2 = max3(m2, sc[1][14], sc[1][15]);
+        m0 = max3(m0, m1, m2);
+        float a = max3(m0, m3, m3), bb = a;
         ADVGRPO_SWAP32(a, bb);
-        return d128_max3(a, bb, bb);
+        return max3(a, bb, bb);
     };
     auto mask_tail = [&](f32x16 (&sc)[2], int kv0) __attribute__((always_inline)) {
         if (kv0 + ATT_KB > (VARLEN ? L : p.Skv)) {
@@ -292,7 +276,7 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
         constexpr bool HAVE_PV = !decltype(first_tag)::value;
         constexpr int VRD = ((J4 + 3) & 3) * D128_TILE, KRD = ((J4 + 1) & 3) * D128_TILE;
         const bool more_dma = j + 2 < nt;       // (the last tile still multiplies a K tile: bundle nt - 1's copy of K(nt - 1), result unused)
-        if ((D128_VAR & 128) != 0 && more_dma) bundle(j + 2, d128_int<J4 + 2>{});
+        if ((D128_VAR & 128) != 0 && more_dma) bundle(j + 2, int_c<J4 + 2>{});
         if (j == nt - 1) mask_tail(s, j * ATT_KB);
         auto operand = [&](auto s_tag) __attribute__((always_inline)) {
             constexpr int sl = decltype(s_tag)::value;
@@ -304,7 +288,7 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
         bf16x8_t a[NA];
         static_for<AH>([&](auto i_tag) __attribute__((always_inline)) {
             constexpr int i = decltype(i_tag)::value;
-            if constexpr (has_operand(i)) a[i] = operand(d128_int<i>{});
+            if constexpr (has_operand(i)) a[i] = operand(int_c<i>{});
         });
         f32x2 x[2], e[2];
         auto slot = [&](auto s_tag) __attribute__((always_inline)) {
@@ -317,22 +301,22 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
                     // so the first two operands cannot be read ahead of it)
                     static_for<AH>([&](auto i_tag) __attribute__((always_inline)) {
                         constexpr int i = 16 + decltype(i_tag)::value;
-                        a[i % NA] = operand(d128_int<i>{});
+                        a[i % NA] = operand(int_c<i>{});
                     });
                 }
                 if constexpr ((D128_VAR & 2) != 0) __builtin_amdgcn_s_setprio(1);
             }
             D128_SB();
             if constexpr (sl < 16) {
-                if constexpr (HAVE_PV) o[sl & 3] = D128_MFMA(a[sl % NA], __builtin_bit_cast(bf16x8_t, pp[sl >> 2]), o[sl & 3]);
+                if constexpr (HAVE_PV) o[sl & 3] = ADVGRPO_MFMA32(a[sl % NA], __builtin_bit_cast(bf16x8_t, pp[sl >> 2]), o[sl & 3]);
             } else if constexpr (sl < 32) {
-                s[sl & 1] = D128_MFMA(a[sl % NA], qf[(sl - 16) >> 1], sl < 18 ? zero16 : s[sl & 1]);
+                s[sl & 1] = ADVGRPO_MFMA32(a[sl % NA], qf[(sl - 16) >> 1], sl < 18 ? zero16 : s[sl & 1]);
             }
             if constexpr (has_operand(sl + AH) && !(D128_STAGGER && sl < 16 && sl + AH >= 16)) {
-                a[(sl + AH) % NA] = operand(d128_int<(sl + AH) % 32>{});
+                a[(sl + AH) % NA] = operand(int_c<(sl + AH) % 32>{});
             }
             if constexpr (sl >= 2 && sl - 2 < 16) {
-                pn[(sl - 2) >> 2][(sl - 2) & 3] = d128_cvt_pk(e[sl & 1][0], e[sl & 1][1]);
+                pn[(sl - 2) >> 2][(sl - 2) & 3] = cvt_pk_bf16(e[sl & 1][0], e[sl & 1][1]);
                 D128_PIN(pn[(sl - 2) >> 2][(sl - 2) & 3]);
                 lsum[sl & 1] += e[sl & 1];
                 D128_PIN(lsum[sl & 1]);
@@ -340,7 +324,7 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
             if constexpr (sl >= 1 && sl - 1 < 16) { e[(sl - 1) & 1] = pair_exp(x[(sl - 1) & 1]); D128_PIN(e[(sl - 1) & 1]); }
             if constexpr (sl < 16) { x[sl & 1] = pair_x(sl); D128_PIN(x[sl & 1]); }
             if constexpr ((D128_VAR & 128) == 0 && sl >= 18 && sl < 32 && ((sl - 18) & 3) == 0) {
-                if (more_dma) bundle_piece(j + 2, d128_int<J4 + 2>{}, d128_int<(sl - 18) / 4>{});
+                if (more_dma) bundle_piece(j + 2, int_c<J4 + 2>{}, int_c<(sl - 18) / 4>{});
             }
         };
         static_for<32>(slot);
@@ -356,23 +340,21 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
         for (int kk = 0; kk < 4; ++kk) {
             const bf16x8_t pb = __builtin_bit_cast(bf16x8_t, pp[kk]);
 #pragma unroll
-            for (int db = 0; db < 4; ++db) o[db] = D128_MFMA(vfrag(imm + kk * 4096, db), pb, o[db]);
+            for (int db = 0; db < 4; ++db) o[db] = ADVGRPO_MFMA32(vfrag(imm + kk * 4096, db), pb, o[db]);
         }
     };
-    typedef std::integral_constant<bool, true> first_t;
-    typedef std::integral_constant<bool, false> steady_t;
     // P(j) lives in pA for even j, pB for odd j; the body is unrolled over the ring period
-    tile(d128_int<0>{}, first_t{}, 0, pB, pA);
+    tile(int_c<0>{}, true_c{}, 0, pB, pA);
     int j = 1;
     for (; j + 4 <= nt; j += 4) {
-        tile(d128_int<1>{}, steady_t{}, j, pA, pB);
-        tile(d128_int<2>{}, steady_t{}, j + 1, pB, pA);
-        tile(d128_int<3>{}, steady_t{}, j + 2, pA, pB);
-        tile(d128_int<0>{}, steady_t{}, j + 3, pB, pA);
+        tile(int_c<1>{}, false_c{}, j, pA, pB);
+        tile(int_c<2>{}, false_c{}, j + 1, pB, pA);
+        tile(int_c<3>{}, false_c{}, j + 2, pA, pB);
+        tile(int_c<0>{}, false_c{}, j + 3, pB, pA);
     }
-    if (j < nt) { tile(d128_int<1>{}, steady_t{}, j, pA, pB); ++j; }
-    if (j < nt) { tile(d128_int<2>{}, steady_t{}, j, pB, pA); ++j; }
-    if (j < nt) { tile(d128_int<3>{}, steady_t{}, j, pA, pB); ++j; }
+    if (j < nt) { tile(int_c<1>{}, false_c{}, j, pA, pB); ++j; }
+    if (j < nt) { tile(int_c<2>{}, false_c{}, j, pB, pA); ++j; }
+    if (j < nt) { tile(int_c<3>{}, false_c{}, j, pA, pB); ++j; }
     // the last tile's P V (its probabilities: pA for an even tile index, pB for an odd one; V ring slot (nt - 1) & 3)
     switch ((nt - 1) & 3) {
         case 0: tile_pv(0 * D128_TILE, pA); break;
@@ -402,14 +384,14 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
             float m_run = -INFINITY, l_run = 0.f;
             for (int t = 0; t < nt; ++t) {
                 __builtin_amdgcn_s_barrier();
-                dma_k(t, d128_int<0>{}, d128_int<0>{}); dma_k(t, d128_int<0>{}, d128_int<1>{});
-                dma_v(t, d128_int<0>{}, d128_int<0>{}); dma_v(t, d128_int<0>{}, d128_int<1>{});
+                dma_k(t, int_c<0>{}, int_c<0>{}); dma_k(t, int_c<0>{}, int_c<1>{});
+                dma_v(t, int_c<0>{}, int_c<0>{}); dma_v(t, int_c<0>{}, int_c<1>{});
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
 #pragma unroll
                 for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
-                    for (int kb = 0; kb < 2; ++kb) s[kb] = D128_MFMA(kfrag(kb * 8192, ks), qf[ks], ks == 0 ? zero16 : s[kb]);
+                    for (int kb = 0; kb < 2; ++kb) s[kb] = ADVGRPO_MFMA32(kfrag(kb * 8192, ks), qf[ks], ks == 0 ? zero16 : s[kb]);
                 mask_tail(s, t * ATT_KB);
                 const float m_new = fmaxf(m_run, row_max(s) * p.scale_log2e);
                 const float f = __builtin_amdgcn_exp2f(m_run - m_new);
@@ -424,7 +406,7 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     const f32x2 e = pair_exp(pair_x(i));
-                    pA[i >> 2][i & 3] = d128_cvt_pk(e[0], e[1]);
+                    pA[i >> 2][i & 3] = cvt_pk_bf16(e[0], e[1]);
                     lsum[i & 1] += e;
                 }
                 tile_pv(0, pA);
@@ -451,8 +433,8 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             uint2 pk;
-            pk.x = d128_cvt_pk(o[db][4 * i] * inv, o[db][4 * i + 1] * inv);
-            pk.y = d128_cvt_pk(o[db][4 * i + 2] * inv, o[db][4 * i + 3] * inv);
+            pk.x = cvt_pk_bf16(o[db][4 * i] * inv, o[db][4 * i + 1] * inv);
+            pk.y = cvt_pk_bf16(o[db][4 * i + 2] * inv, o[db][4 * i + 3] * inv);
             // d = db*32 + 8 i + 4 hi .. + 3  ->  16-byte chunk db*4 + i, 8-byte half hi
             *reinterpret_cast<uint2*>(ob + ql * 256 + (((db * 4 + i) ^ (ql & 15)) << 4) + hi * 8) = pk;
         }

@@ -223,7 +223,6 @@ __global__ __launch_bounds__(256) void attention_fwd_gqa_kernel(const GqaParams 
                     const bf16_t* a1 = a0 + 16 * PITCH;
                     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
                     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a1));
-                    typedef __attribute__((ext_vector_type(8))) short s16x8;
                     const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                     const bf16x8_t vf = __builtin_bit_cast(bf16x8_t, both);
 #pragma unroll

@@ -52,32 +52,10 @@ __device__ unsigned long long g_pipe_fallbacks = 0;
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// (through the compiler, which fuses the pair into v_max3_f32: as an asm statement its reads of the score accumulators were
-// not padded against the MFMAs that had just written them, and the reference maximum came out of half-written registers)
-__device__ __forceinline__ float att_max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-// two f32 -> packed bf16 (v_cvt_pk_bf16_f32).  Through the compiler, NOT inline asm: the packed probabilities are written
-// into registers that MFMAs issued a slot earlier may still be reading as their B operand, and the hazard recogniser only
-// pads instructions it knows (an asm statement here produced wrong probabilities for half of the query lanes).
-__device__ __forceinline__ uint32_t att_cvt_pk(float lo, float hi) {
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    const f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
 __device__ __forceinline__ float att_exp2(float x) {
     if constexpr ((ATT_ABL & 2) != 0) return x * 0.75f;
     return __builtin_amdgcn_exp2f(x);
 }
-
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
-#define ATT_SB() __builtin_amdgcn_sched_barrier(0)
-// keeps a value (and the instructions that made it) in the slot where it was written: without it the row-sum adds are sunk
-// out of the iteration (their result is only read at the very end) and all 32 probabilities stay live across it
-#define ATT_PIN(x) asm volatile("" : "+v"(x))
-#define ATT_MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
 
 }  // namespace
 
@@ -125,11 +103,11 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_pipe_kernel(const AttnPa
     }
     const int64_t k_half = (int64_t)32 * p.ldk * 2, v_half = (int64_t)32 * p.ldv * 2;
     const int64_t k_step = (int64_t)ATT_KB * p.ldk * 2, v_step = (int64_t)ATT_KB * p.ldv * 2;      // bytes per tile
-    const uint32_t k_lds = (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)(Kr)) + wave * 1024;
+    const uint32_t k_lds = lds_addr(Kr) + wave * 1024;
     const uint32_t v_lds = k_lds + 3 * TILE_B;
     auto dma = [&](const char* base, uint32_t off, uint32_t lds) __attribute__((always_inline)) {
         if constexpr ((ATT_ABL & 8) != 0) return;
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(lds) : "memory");
+        lds_dma16(base, off, lds);
     };
     // a ragged last tile clamps the rows past the end of the sequence to its last row (their scores are masked)
     auto stage_k = [&](int slot, int t) __attribute__((always_inline)) {
@@ -183,7 +161,6 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_pipe_kernel(const AttnPa
     v_off[0] = vb + (b3 ? 64 : 0);
     v_off[1] = vb + (b3 ? 0 : 64);
 
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
     // fragment reads at byte offset `off` (slot base + block offset: an immediate when the slot is a compile-time constant)
     auto kfrag = [&](int off, int ks) __attribute__((always_inline)) {
         if constexpr ((ATT_ABL & 4) != 0) return qf[ks];
@@ -275,27 +252,27 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_pipe_kernel(const AttnPa
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb) sA[kb] = ATT_MFMA32(kfrag(kb * 4096, ks), qf[ks], sA[kb]);
+        for (int kb = 0; kb < 2; ++kb) sA[kb] = ADVGRPO_MFMA32(kfrag(kb * 4096, ks), qf[ks], sA[kb]);
 
     auto row_max = [&](const f32x16 (&sc)[2]) __attribute__((always_inline)) {
-        float m0 = att_max3(sc[0][0], sc[0][1], sc[0][2]);
-        float m1 = att_max3(sc[0][3], sc[0][4], sc[0][5]);
-        float m2 = att_max3(sc[1][0], sc[1][1], sc[1][2]);
-        float m3 = att_max3(sc[1][3], sc[1][4], sc[1][5]);
-        m0 = att_max3(m0, sc[0][6], sc[0][7]);
-        m1 = att_max3(m1, sc[0][8], sc[0][9]);
-        m2 = att_max3(m2, sc[1][6], sc[1][7]);
-        m3 = att_max3(m3, sc[1][8], sc[1][9]);
-        m0 = att_max3(m0, sc[0][10], sc[0][11]);
-        m1 = att_max3(m1, sc[0][12], sc[0][13]);
-        m2 = att_max3(m2, sc[1][10], sc[1][11]);
-        m3 = att_max3(m3, sc[1][12], sc[1][13]);
-        m0 = att_max3(m0, sc[0][14], sc[0][15]);
-        m2 = att_max3(m2, sc[1][14], sc[1][15]);
-        m0 = att_max3(m0, m1, m2);
-        float a = att_max3(m0, m3, m3), b = a;
+        float m0 = max3(sc[0][0], sc[0][1], sc[0][2]);
+        float m1 = max3(sc[0][3], sc[0][4], sc[0][5]);
+        float m2 = max3(sc[1][0], sc[1][1], sc[1][2]);
+        float m3 = max3(sc[1][3], sc[1][4], sc[1][5]);
+        m0 = max3(m0, sc[0][6], sc[0][7]);
+        m1 = max3(m1, sc[0][8], sc[0][9]);
+        m2 = max3(m2, sc[1][6], sc[1][7]);
+        m3 = max3(m3, sc[1][8], sc[1][9]);
+        m0 = max3(m0, sc[0][10], sc[0][11]);
+        m1 = max3(m1, sc[0][12], sc[0][13]);
+        m2 = max3(m2, sc[1][10], sc[1][11]);
+        m3 = max3(m3, sc[1][12], sc[1][13]);
+        m0 = max3(m0, sc[0][14], sc[0][15]);
+        m2 = max3(m2, sc[1][14], sc[1][15]);
+        m0 = max3(m0, m1, m2);
+        float a = max3(m0, m3, m3), b = a;
         ADVGRPO_SWAP32(a, b);
-        return att_max3(a, b, b);
+        return max3(a, b, b);
     };
     // score pair i (0..15) of a tile = elements 2i, 2i+1 of the lane's 32 scores, in log2 units relative to the reference max
     auto pair_x = [&](const f32x16 (&sc)[2], int i) __attribute__((always_inline)) {
@@ -313,7 +290,7 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_pipe_kernel(const AttnPa
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const f32x2 e = pair_exp(pair_x(sc, i));
-            pn[i >> 2][i & 3] = att_cvt_pk(e[0], e[1]);
+            pn[i >> 2][i & 3] = cvt_pk_bf16(e[0], e[1]);
             lsum[i & 1] += e;
         }
     };
@@ -322,8 +299,8 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_pipe_kernel(const AttnPa
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
             const bf16x8_t pb = __builtin_bit_cast(bf16x8_t, pp[kk]);
-            o[0] = ATT_MFMA32(vfrag(vt + kk * 2048, 0), pb, o[0]);
-            o[1] = ATT_MFMA32(vfrag(vt + kk * 2048, 1), pb, o[1]);
+            o[0] = ADVGRPO_MFMA32(vfrag(vt + kk * 2048, 0), pb, o[0]);
+            o[1] = ADVGRPO_MFMA32(vfrag(vt + kk * 2048, 1), pb, o[1]);
         }
     };
     auto mask_tail = [&](f32x16 (&sc)[2], int kv0) __attribute__((always_inline)) {
@@ -372,39 +349,39 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_pipe_kernel(const AttnPa
             else return vfrag(VRD + ((s - 8) >> 1) * 2048, (s - 8) & 1);
         };
         bf16x8_t a[3];
-        a[0] = operand(std::integral_constant<int, 0>{});
-        a[1] = operand(std::integral_constant<int, 1>{});
+        a[0] = operand(int_c<0>{});
+        a[1] = operand(int_c<1>{});
         f32x2 x[2], e[2];
         auto slot = [&](auto s_tag) __attribute__((always_inline)) {
             constexpr int s = decltype(s_tag)::value;
-            ATT_SB();
+            ADVGRPO_SB();
             if constexpr (s < 8) {
-                if constexpr ((s >> 1) == 0) sn[s & 1] = ATT_MFMA32(a[s % 3], qf[0], zero16);
-                else sn[s & 1] = ATT_MFMA32(a[s % 3], qf[s >> 1], sn[s & 1]);
+                if constexpr ((s >> 1) == 0) sn[s & 1] = ADVGRPO_MFMA32(a[s % 3], qf[0], zero16);
+                else sn[s & 1] = ADVGRPO_MFMA32(a[s % 3], qf[s >> 1], sn[s & 1]);
             } else if constexpr (HAVE_PV && s < 16) {
-                o[(s - 8) & 1] = ATT_MFMA32(a[s % 3], __builtin_bit_cast(bf16x8_t, pp[(s - 8) >> 1]), o[(s - 8) & 1]);
+                o[(s - 8) & 1] = ADVGRPO_MFMA32(a[s % 3], __builtin_bit_cast(bf16x8_t, pp[(s - 8) >> 1]), o[(s - 8) & 1]);
             }
-            if constexpr (needs_operand(s + 2)) a[(s + 2) % 3] = operand(std::integral_constant<int, (s + 2) % 32>{});
+            if constexpr (needs_operand(s + 2)) a[(s + 2) % 3] = operand(int_c<(s + 2) % 32>{});
             // (the empty asm statements keep each piece in its slot: without them the whole softmax is scheduled in front of
             // the first MFMA -- sched_barrier alone did not hold it)
             if constexpr (s >= 2 && s - 2 < 16) {
-                pn[(s - 2) >> 2][(s - 2) & 3] = att_cvt_pk(e[s & 1][0], e[s & 1][1]);
-                ATT_PIN(pn[(s - 2) >> 2][(s - 2) & 3]);
-                if constexpr ((ATT_ABL & 64) == 0) { lsum[s & 1] += e[s & 1]; ATT_PIN(lsum[s & 1]); }
+                pn[(s - 2) >> 2][(s - 2) & 3] = cvt_pk_bf16(e[s & 1][0], e[s & 1][1]);
+                ADVGRPO_PIN(pn[(s - 2) >> 2][(s - 2) & 3]);
+                if constexpr ((ATT_ABL & 64) == 0) { lsum[s & 1] += e[s & 1]; ADVGRPO_PIN(lsum[s & 1]); }
             }
-            if constexpr (s >= 1 && s - 1 < 16) { e[(s - 1) & 1] = pair_exp(x[(s - 1) & 1]); ATT_PIN(e[(s - 1) & 1]); }
-            if constexpr (s < 16) { x[s & 1] = pair_x(sc, s); ATT_PIN(x[s & 1]); }
+            if constexpr (s >= 1 && s - 1 < 16) { e[(s - 1) & 1] = pair_exp(x[(s - 1) & 1]); ADVGRPO_PIN(e[(s - 1) & 1]); }
+            if constexpr (s < 16) { x[s & 1] = pair_x(sc, s); ADVGRPO_PIN(x[s & 1]); }
         };
-        slot(std::integral_constant<int, 0>{}); slot(std::integral_constant<int, 1>{});
-        slot(std::integral_constant<int, 2>{}); slot(std::integral_constant<int, 3>{});
-        slot(std::integral_constant<int, 4>{}); slot(std::integral_constant<int, 5>{});
-        slot(std::integral_constant<int, 6>{}); slot(std::integral_constant<int, 7>{});
-        slot(std::integral_constant<int, 8>{}); slot(std::integral_constant<int, 9>{});
-        slot(std::integral_constant<int, 10>{}); slot(std::integral_constant<int, 11>{});
-        slot(std::integral_constant<int, 12>{}); slot(std::integral_constant<int, 13>{});
-        slot(std::integral_constant<int, 14>{}); slot(std::integral_constant<int, 15>{});
-        slot(std::integral_constant<int, 16>{}); slot(std::integral_constant<int, 17>{});     // (the last two packs, no MFMA)
-        ATT_SB();
+        slot(int_c<0>{}); slot(int_c<1>{});
+        slot(int_c<2>{}); slot(int_c<3>{});
+        slot(int_c<4>{}); slot(int_c<5>{});
+        slot(int_c<6>{}); slot(int_c<7>{});
+        slot(int_c<8>{}); slot(int_c<9>{});
+        slot(int_c<10>{}); slot(int_c<11>{});
+        slot(int_c<12>{}); slot(int_c<13>{});
+        slot(int_c<14>{}); slot(int_c<15>{});
+        slot(int_c<16>{}); slot(int_c<17>{});     // (the last two packs, no MFMA)
+        ADVGRPO_SB();
     };
 
     // ---- main loop: iterations 0 .. nt - 2.  The ring phase has period 3 and the score / probability buffers alternate by
@@ -412,8 +389,6 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_pipe_kernel(const AttnPa
     // values); the up to five left-over iterations run one at a time with the ring phase in a register and the buffers
     // copied back to their names.  Invariant between iterations (nt >= 2): current tile's scores in sB, previous tile's
     // probabilities in pA.
-    typedef std::integral_constant<bool, true> first_t;
-    typedef std::integral_constant<bool, false> steady_t;
 #ifndef ATT_PRIO
 #define ATT_PRIO 0      // experiment (scripts/probes/r6_job31.sh): 1 / 2 = s_setprio 1 / 3 over the main loop, 3 = static priority by workgroup parity: no gain, see LABNOTES 9
 #endif
@@ -421,19 +396,19 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_pipe_kernel(const AttnPa
     if constexpr (ATT_PRIO == 2) __builtin_amdgcn_s_setprio(3);
     if constexpr (ATT_PRIO == 3) { if (blockIdx.x & 1) __builtin_amdgcn_s_setprio(1); }
     if (nt >= 2) {
-        iteration(0, first_t{}, 0, sA, sB, pB, pA);
+        iteration(0, true_c{}, 0, sA, sB, pB, pA);
         int j = 1;
         const int nfull = nt - 1;
         for (; j + 6 <= nfull; j += 6) {
-            iteration(1, steady_t{}, j, sB, sA, pA, pB);
-            iteration(2, steady_t{}, j + 1, sA, sB, pB, pA);
-            iteration(0, steady_t{}, j + 2, sB, sA, pA, pB);
-            iteration(1, steady_t{}, j + 3, sA, sB, pB, pA);
-            iteration(2, steady_t{}, j + 4, sB, sA, pA, pB);
-            iteration(0, steady_t{}, j + 5, sA, sB, pB, pA);
+            iteration(1, false_c{}, j, sB, sA, pA, pB);
+            iteration(2, false_c{}, j + 1, sA, sB, pB, pA);
+            iteration(0, false_c{}, j + 2, sB, sA, pA, pB);
+            iteration(1, false_c{}, j + 3, sA, sB, pB, pA);
+            iteration(2, false_c{}, j + 4, sB, sA, pA, pB);
+            iteration(0, false_c{}, j + 5, sA, sB, pB, pA);
         }
         for (; j < nfull; ++j) {
-            iteration(j % 3, steady_t{}, j, sB, sA, pA, pB);
+            iteration(j % 3, false_c{}, j, sB, sA, pA, pB);
             sB[0] = sA[0]; sB[1] = sA[1];
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) pA[kk] = pB[kk];
@@ -465,12 +440,12 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_pipe_kernel(const AttnPa
 #pragma unroll
                     for (int i = 4 * kk; i < 4 * kk + 4; ++i) {
                         const f32x2 e = pair_exp(pair_x(sB, i));
-                        pB[kk][i & 3] = att_cvt_pk(e[0], e[1]);
+                        pB[kk][i & 3] = cvt_pk_bf16(e[0], e[1]);
                         lsum[i & 1] += e;
                     }
                     const bf16x8_t pb = __builtin_bit_cast(bf16x8_t, pB[kk]);
-                    o[0] = ATT_MFMA32(vfrag(vt + kk * 2048, 0), pb, o[0]);
-                    o[1] = ATT_MFMA32(vfrag(vt + kk * 2048, 1), pb, o[1]);
+                    o[0] = ADVGRPO_MFMA32(vfrag(vt + kk * 2048, 0), pb, o[0]);
+                    o[1] = ADVGRPO_MFMA32(vfrag(vt + kk * 2048, 1), pb, o[1]);
                 }
             }
         }
@@ -505,7 +480,7 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_pipe_kernel(const AttnPa
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-                    for (int kb = 0; kb < 2; ++kb) sA[kb] = ATT_MFMA32(kfrag(kb * 4096, ks), qf[ks], sA[kb]);
+                    for (int kb = 0; kb < 2; ++kb) sA[kb] = ADVGRPO_MFMA32(kfrag(kb * 4096, ks), qf[ks], sA[kb]);
                 mask_tail(sA, t * ATT_KB);
                 const float m_new = fmaxf(m_run, row_max(sA) * p.scale_log2e);
                 const float f = att_exp2(m_run - m_new);         // first tile: exp2(-inf) = 0 on zeros
@@ -548,8 +523,8 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_pipe_kernel(const AttnPa
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             uint2 pk;
-            pk.x = att_cvt_pk(o[db][4 * i] * inv, o[db][4 * i + 1] * inv);
-            pk.y = att_cvt_pk(o[db][4 * i + 2] * inv, o[db][4 * i + 3] * inv);
+            pk.x = cvt_pk_bf16(o[db][4 * i] * inv, o[db][4 * i + 1] * inv);
+            pk.y = cvt_pk_bf16(o[db][4 * i + 2] * inv, o[db][4 * i + 3] * inv);
             // d = db*32 + 8 i + 4 hi .. + 3  ->  16-byte chunk db*4 + i, 8-byte half hi
             *reinterpret_cast<uint2*>(ob + eql * 128 + (((db * 4 + i) ^ (eql & 7)) << 4) + ehi * 8) = pk;
         }

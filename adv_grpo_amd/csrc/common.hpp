@@ -160,3 +160,5 @@ __device__ inline void philox_normal4(const Philox& ph, uint64_t ctr, float z[4]
 }
 
 }  // namespace advgrpo
+
+#include "device_prims.hpp"

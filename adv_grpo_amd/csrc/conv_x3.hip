@@ -38,8 +38,6 @@ namespace advgrpo {
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* x3_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* x3_gptr_t;
 
 constexpr int X3_BM = 192, X3_BN = 128, X3_BK = 64;
 #ifndef X3_GRID_M
@@ -159,10 +157,10 @@ __global__ __launch_bounds__(64 * X3_WM * X3_WN, 1) void conv3x3_x3_kernel(const
                                   : p.zero_page + schunk * 8;
             const bf16_t* lo = ok ? hi + 2 * C : hi;                          // [hi | hi | lo]
             char* dst = base + (wave + it * NW) * 1024;
-            __builtin_amdgcn_global_load_lds((x3_gptr_t)hi, (x3_lds_ptr_t)dst, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)hi, (lds_ptr_t)dst, 16, 0, 0);
             // (f16x1 reads the hi pieces only.  Every wait of the k loop allows the WPI * WI most recent requests -- a weight stage -- to be outstanding
             // and nothing older, so leaving the lo requests out changes no count)
-            if constexpr (!X1) __builtin_amdgcn_global_load_lds((x3_gptr_t)lo, (x3_lds_ptr_t)(dst + X3_XPIECE), 16, 0, 0);
+            if constexpr (!X1) __builtin_amdgcn_global_load_lds((gptr_t)lo, (lds_ptr_t)(dst + X3_XPIECE), 16, 0, 0);
         }
     };
     // strided form: the pixel stage of k-tile kt = (g, kx) -- LDS row j = input pixel (2 y + ky, 2 x + kx) of output pixel m0 - 1 + j
@@ -178,8 +176,8 @@ __global__ __launch_bounds__(64 * X3_WM * X3_WN, 1) void conv3x3_x3_kernel(const
             const bf16_t* hi = ok ? p.A + a_img[it] + ((int64_t)yy * wi2 + xx) * p.Cin + c0 + schunk * 8 : p.zero_page + schunk * 8;
             const bf16_t* lo = ok ? hi + 2 * C : hi;
             char* dst = smem + (wave + it * NW) * 1024;
-            __builtin_amdgcn_global_load_lds((x3_gptr_t)hi, (x3_lds_ptr_t)dst, 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((x3_gptr_t)lo, (x3_lds_ptr_t)(dst + X3_XPIECE), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)hi, (lds_ptr_t)dst, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)lo, (lds_ptr_t)(dst + X3_XPIECE), 16, 0, 0);
         }
     };
     (void)stage_x; (void)stage_x_s2;             // (one of the two per instantiation)
@@ -191,8 +189,8 @@ __global__ __launch_bounds__(64 * X3_WM * X3_WN, 1) void conv3x3_x3_kernel(const
         for (int it = 0; it < WI; ++it) {
             char* dst = base + (wave + it * NW) * 1024;
             const bf16_t* wh = w_src[it] + (int64_t)tap * (F16 ? C : p.Cin) + c0;   // per tap [hi | lo | hi]; F16: one piece per tap
-            __builtin_amdgcn_global_load_lds((x3_gptr_t)wh, (x3_lds_ptr_t)dst, 16, 0, 0);
-            if constexpr (!F16) __builtin_amdgcn_global_load_lds((x3_gptr_t)(wh + C), (x3_lds_ptr_t)(dst + WPIECE), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)wh, (lds_ptr_t)dst, 16, 0, 0);
+            if constexpr (!F16) __builtin_amdgcn_global_load_lds((gptr_t)(wh + C), (lds_ptr_t)(dst + WPIECE), 16, 0, 0);
         }
     };
 
@@ -232,7 +230,7 @@ __global__ __launch_bounds__(64 * X3_WM * X3_WN, 1) void conv3x3_x3_kernel(const
     else stage_x(0);
     stage_w(0, 0, 0);
     stage_w(1, 0, 1);
-    asm volatile("s_waitcnt vmcnt(%0)" : : "n"(WPI * WI) : "memory");
+    wait_vm<WPI * WI>();
     __builtin_amdgcn_s_barrier();
     static_assert(FM + FN <= 15 && (F16 || 3 * FN <= 15) && (!F16 || 2 * FM + FN <= 15), "lgkmcnt counts at most 15 reads in flight");
     auto product = [&](const bf16x8_t (&a)[FM], const bf16x8_t (&b)[FN]) __attribute__((always_inline)) {
@@ -453,7 +451,7 @@ __global__ __launch_bounds__(64 * X3_WM * X3_WN, 1) void conv3x3_x3_kernel(const
                 product(ah1, bh1);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (more) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(WPI * WI) : "memory");
+            if (more) wait_vm<WPI * WI>();
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         });

@@ -50,11 +50,7 @@ __device__ __forceinline__ void w4_setup(W4Tile& t, const GemmParams& pr, int id
         for (int it = 0; it < 2; ++it) {
             int r = t.m0 + sub * 64 + (wave + it * 4) * 8 + lrow;
             r = r < p->M ? r : p->M - 1;
-            int64_t ar = r;
-            if (p->a_seg_rows > 0) {
-                const int bi = r / p->a_seg_rows;
-                ar = (int64_t)bi * p->a_seg_stride + p->a_seg_off + (r - bi * p->a_seg_rows);
-            }
+            const int64_t ar = seg_row(r, p->a_seg_rows, p->a_seg_stride, p->a_seg_off);
             t.a_off[sub][it] = (uint32_t)((ar * p->lda + schunk * 8) * 2);
         }
         {   // slot row sr = (wave + 4 it) * 8 + lrow -> column (sr >> 5) * 64 + sub * 32 + (sr & 31): it adds 64 columns
@@ -72,14 +68,14 @@ __device__ __forceinline__ void w4_stage_a(const W4Tile& t, char* smem, int wave
     char* base = smem + slot * W4_AITEM;
     const char* src = t.a_bytes + kt * (W4_BK * 2);
 #pragma unroll
-    for (int it = 0; it < 2; ++it) p8_dma16(src, t.a_off[sub][it], lds_addr(base + (wave + it * 4) * 1024));
+    for (int it = 0; it < 2; ++it) lds_dma16(src, t.a_off[sub][it], lds_addr(base + (wave + it * 4) * 1024));
 }
 __device__ __forceinline__ void w4_stage_w(const W4Tile& t, char* smem, int wave, int slot, int sub, int kt) {
     if (kt >= t.nk) return;
     char* base = smem + W4_W_REGION + slot * W4_WITEM;
     const char* src = t.w_bytes + kt * (W4_BK * 2);
 #pragma unroll
-    for (int it = 0; it < 4; ++it) p8_dma16(src + it * t.w_step, t.b_off[sub], lds_addr(base + (wave + it * 4) * 1024));
+    for (int it = 0; it < 4; ++it) lds_dma16(src + it * t.w_step, t.b_off[sub], lds_addr(base + (wave + it * 4) * 1024));
 }
 
 }  // namespace

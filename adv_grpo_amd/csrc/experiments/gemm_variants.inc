@@ -41,11 +41,7 @@ __device__ __forceinline__ void gemm_bf16_pipe_body(const GemmParams& p, const i
     for (int it = 0; it < A_INST; ++it) {
         int r = m0 + (wave + it * NW) * 16 + lrow;
         r = r < p.M ? r : p.M - 1;
-        int64_t ar = r;
-        if (p.a_seg_rows > 0) {
-            const int bi = r / p.a_seg_rows;
-            ar = (int64_t)bi * p.a_seg_stride + p.a_seg_off + (r - bi * p.a_seg_rows);
-        }
+        const int64_t ar = seg_row(r, p.a_seg_rows, p.a_seg_stride, p.a_seg_off);
         a_src[it] = A + ar * p.lda + schunk * 8;
     }
 #pragma unroll
@@ -83,8 +79,8 @@ __device__ __forceinline__ void gemm_bf16_pipe_body(const GemmParams& p, const i
     for (int kt = 0; kt < nk; ++kt) {
         // tile kt must have landed: allow the younger tiles (at most AHEAD) to stay in flight
         const int ahead = min(nk - 1 - kt, AHEAD);
-        if (ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LOADS) : "memory");
-        else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
+        if (ahead >= 2) wait_vm<2 * LOADS>();
+        else if (ahead == 1) wait_vm<LOADS>();
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         // the slot of tile kt-1 is free now (every wave passed the barrier after reading it): refill it
@@ -177,11 +173,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const GemmParams p) {
     for (int it = 0; it < A_INST; ++it) {
         int r = m0 + (wave + it * NW) * 16 + lrow;
         r = r < p.M ? r : p.M - 1;
-        int64_t ar = r;
-        if (p.a_seg_rows > 0) {
-            const int bi = r / p.a_seg_rows;
-            ar = (int64_t)bi * p.a_seg_stride + p.a_seg_off + (r - bi * p.a_seg_rows);
-        }
+        const int64_t ar = seg_row(r, p.a_seg_rows, p.a_seg_stride, p.a_seg_off);
         a_src[it] = A + ar * p.lda + schunk * 8;
     }
 #pragma unroll
@@ -211,7 +203,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const GemmParams p) {
     const int nk = (p.debug & 8) ? 2 : p.K / BK;
     stage(0, 0);
     if (nk > 1) stage(1, 1);
-    if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
+    if (nk > 1) wait_vm<LOADS>();
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                     // tile 0 is complete for everybody
     if (grp == 1) __builtin_amdgcn_s_barrier();       // stagger: group 1 runs one segment behind
@@ -231,7 +223,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const GemmParams p) {
         slot = slot + 1 == NS ? 0 : slot + 1;
         slot2 = slot2 + 1 == NS ? 0 : slot2 + 1;
         if (grp == 1) {   // tile kt+1 is first read right after the next barrier (by group 0)
-            if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
+            if (kt + 2 < nk) wait_vm<LOADS>();
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             // with a 3-slot ring group 0 refills the slot of tile kt (= slot of tile kt+3) right after the next
             // barrier: this group's fragment reads of it must have completed, not just been issued
@@ -249,7 +241,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const GemmParams p) {
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j], af[i], acc[i][j], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
         if (grp == 0) {
-            if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
+            if (kt + 2 < nk) wait_vm<LOADS>();
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         __builtin_amdgcn_s_barrier();

@@ -77,12 +77,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
             a_img[it] = (int64_t)bi * (p.Hout >> p.ups) * (p.Wout >> p.ups) * p.Cin;
             a_src[it] = nullptr;
         } else {
-            int64_t ar = r;
-            if (p.a_seg_rows > 0) {
-                const int bi = r / p.a_seg_rows;
-                ar = (int64_t)bi * p.a_seg_stride + p.a_seg_off + (r - bi * p.a_seg_rows);
-            }
-            a_src[it] = A + ar * p.lda + schunk * 8;
+            a_src[it] = A + seg_row(r, p.a_seg_rows, p.a_seg_stride, p.a_seg_off) * p.lda + schunk * 8;
         }
     }
 #pragma unroll

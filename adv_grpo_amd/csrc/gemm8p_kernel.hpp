@@ -18,15 +18,6 @@ constexpr int P8_BUF = 4 * P8_HALF;               // one k-tile buffer: A sub 0,
 constexpr int P8_LDS = 2 * P8_BUF;                // 128 KiB
 constexpr int P8_SCRATCH = 2 * 16 * 64 * 4;       // per-wave epilogue scratch: 2 slabs of 16 rows x 64 f32, inside buffer 1
 
-// One LDS-DMA instruction: 64 lanes x 16 bytes from (uniform base + per-lane 32-bit offset) to LDS [m0 .. m0 + 1 KiB).
-// Hand-written because the builtin form keeps every per-lane source as a 64-bit VGPR pair and re-adds the k offset on the
-// VALU: 24 VGPRs and 8 v_lshl_add_u64 per k-tile more than the SGPR-base form, enough to spill inside the main loop.
-__device__ __forceinline__ void p8_dma16(const char* base, uint32_t off, uint32_t lds) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(lds) : "memory");
-}
-__device__ __forceinline__ uint32_t lds_addr(const char* p) {
-    return (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)(p));
-}
 // The lane id, re-derived where it is needed (two VALU instructions) instead of kept live: held across the k loop it was
 // spilled, and each reload at the tile boundary was a scratch-memory load followed by s_waitcnt vmcnt(0) -- 18 serialised
 // memory round trips made up most of the ~2.5-3.5k cycles a wave spent between two tiles.
@@ -79,11 +70,7 @@ __device__ __forceinline__ void p8_setup(P8Tile& t, const GemmParams& pr, int id
             const int sr = (wave + it * 8) * 8 + lrow;                    // slot row of this lane's 16 bytes
             int r = t.m0 + (sr >> 6) * 128 + sub * 64 + (sr & 63);
             r = r < p->M ? r : p->M - 1;
-            int64_t ar = r;
-            if (p->a_seg_rows > 0) {
-                const int bi = r / p->a_seg_rows;
-                ar = (int64_t)bi * p->a_seg_stride + p->a_seg_off + (r - bi * p->a_seg_rows);
-            }
+            const int64_t ar = seg_row(r, p->a_seg_rows, p->a_seg_stride, p->a_seg_off);
             t.a_off[sub][it] = (uint32_t)(ar * p->lda * es + schunk * 16);
             int n = t.n0 + (sr >> 5) * 64 + sub * 32 + (sr & 31);
             n = n < p->N ? n : p->N - 1;
@@ -98,7 +85,7 @@ __device__ __forceinline__ void p8_stage(const P8Tile& t, char* smem, int wave, 
     const char* src = (which < 2 ? t.a_bytes : t.w_bytes) + kt * (P8_BK * 2);   // uniform
     const uint32_t* off = which < 2 ? t.a_off[which] : t.b_off[which - 2];
 #pragma unroll
-    for (int it = 0; it < 2; ++it) p8_dma16(src, off[it], lds_addr(base + (wave + it * 8) * 1024));
+    for (int it = 0; it < 2; ++it) lds_dma16(src, off[it], lds_addr(base + (wave + it * 8) * 1024));
 }
 
 // Fused epilogue.  Same arithmetic, in the same order, as gemm_epilogue_rows (gemm_device.hpp) -- results are bit-identical to
@@ -133,7 +120,6 @@ enum { EPI_GENERIC = -1, F_BIAS = 1, F_RMS = 2 /* per-head QK RMSNorm */, F_GELU
 enum { EPI_PLAIN = 0, EPI_BIAS = F_BIAS, EPI_BIAS_RMS = F_BIAS | F_RMS, EPI_BIAS_GELU = F_BIAS | F_GELU, EPI_BIAS_GATE_RES = F_BIAS | F_GATE_RES,
        EPI_BIAS_GELU_AUX = F_BIAS | F_GELU | F_AUX_OUT, EPI_DGELU = F_DGELU };
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // which classes write their output tile with streaming (nt) stores: 0 all (product), 1 all but gate + residual (its output is the next
 // LayerNorm's input), 2 none  -- A/B knob of scripts/probes/rollout_ab_inprocess.py builds
 #ifndef P8_NT_MODE
@@ -145,17 +131,16 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 typedef const __attribute__((address_space(1))) char* p8_gcptr;
 typedef __attribute__((address_space(1))) char* p8_gptr;
-typedef uint32_t p8_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 p8_gld16(p8_gcptr base, uint32_t byte_off) {
-    const p8_u32x4 v = *reinterpret_cast<const __attribute__((address_space(1))) p8_u32x4*>(base + byte_off);
+    const u32x4 v = *reinterpret_cast<const __attribute__((address_space(1))) u32x4*>(base + byte_off);
     return uint4{v.x, v.y, v.z, v.w};
 }
 __device__ __forceinline__ void p8_gst16(p8_gptr base, size_t byte_off, const uint4& v) {
-    *reinterpret_cast<__attribute__((address_space(1))) p8_u32x4*>(base + byte_off) = p8_u32x4{v.x, v.y, v.z, v.w};
+    *reinterpret_cast<__attribute__((address_space(1))) u32x4*>(base + byte_off) = u32x4{v.x, v.y, v.z, v.w};
 }
 // streaming (non-temporal) store: the output tile is not read again by this kernel
 __device__ __forceinline__ void p8_gst16_nt(p8_gptr base, size_t byte_off, const uint4& v) {
-    __builtin_nontemporal_store(p8_u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<__attribute__((address_space(1))) p8_u32x4*>(base + byte_off));
+    __builtin_nontemporal_store(u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<__attribute__((address_space(1))) u32x4*>(base + byte_off));
 }
 // a value pinned into scalar registers (opaque to the optimiser from here on)
 template <class T>
@@ -231,12 +216,8 @@ __device__ __forceinline__ void p8_epilogue(const GemmParams& p_in, f32x4 (&acc)
     auto unpack4 = [&](const uint4& q4, f32x2 (&f)[4]) __attribute__((always_inline)) {
         f[0] = up2(q4.x); f[1] = up2(q4.y); f[2] = up2(q4.z); f[3] = up2(q4.w);
     };
-    auto pk2 = [](f32x2 x) __attribute__((always_inline)) {
-        typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(x, bf16x2_t));
-    };
     auto pack4 = [&](const f32x2 (&x)[4]) __attribute__((always_inline)) {
-        return uint4{pk2(x[0]), pk2(x[1]), pk2(x[2]), pk2(x[3])};
+        return uint4{cvt_pk_bf16(x[0]), cvt_pk_bf16(x[1]), cvt_pk_bf16(x[2]), cvt_pk_bf16(x[3])};
     };
     auto ld16 = [](p8_gcptr base, uint32_t elem) __attribute__((always_inline)) { return p8_gld16(base, elem * 2u); };
     // alpha as ONE scalar register for the whole epilogue: left to the compiler the two problems' alphas of a paired launch
@@ -387,7 +368,7 @@ __device__ __forceinline__ void p8_epilogue(const GemmParams& p_in, f32x4 (&acc)
                     float sq = 0.f;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        v[k] = up2(pk2(v[k]));             // the Linear's bf16 output is what gets normalised
+                        v[k] = up2(cvt_pk_bf16(v[k]));             // the Linear's bf16 output is what gets normalised
                         sq += v[k].x * v[k].x;
                         sq += v[k].y * v[k].y;
                     }
@@ -397,7 +378,7 @@ __device__ __forceinline__ void p8_epilogue(const GemmParams& p_in, f32x4 (&acc)
                         if (p.rms_rs_out && (lane & 7) == 0)
                             *reinterpret_cast<__attribute__((address_space(1))) float*>(p.rms_rs_out + ((size_t)orow * p.rms_nheads + hh) * 4) = rs;
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) v[k] = up2(pk2(v[k] * rs)) * rms_w2[k];
+                        for (int k = 0; k < 4; ++k) v[k] = up2(cvt_pk_bf16(v[k] * rs)) * rms_w2[k];
                     }
                 }
                 const uint32_t o_aux = __umul24(orow, (uint32_t)p.ld_aux) + n;

@@ -8,9 +8,6 @@
 
 namespace advgrpo {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gptr_t;
-
 // gelu_tanh(x) = 0.5 x (1 + tanh u), u = sqrt(2/pi) (x + 0.044715 x^3)  ==  x * sigmoid(2u)  ==  x / (1 + 2^(x (C1 + C2 x^2)))
 // with C1 = -2 sqrt(2/pi) log2(e), C2 = 0.044715 C1: one v_exp + one v_rcp, and five other operations written so that the
 // scalar form below and the two-column form of the eight-phase epilogue (gelu_tanh_pk: v_pk_mul / v_pk_fma / v_pk_add on
@@ -25,14 +22,13 @@ __device__ __forceinline__ float gelu_tanh_f32(float x) {
     const float d = __builtin_amdgcn_exp2f(t) + 1.0f;
     return x * __builtin_amdgcn_rcpf(d);
 }
-typedef float gelu_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ gelu_f32x2 gelu_tanh_pk(gelu_f32x2 x) {
+__device__ __forceinline__ f32x2 gelu_tanh_pk(f32x2 x) {
 #pragma clang fp contract(off)
-    gelu_f32x2 t = x * x;
-    t = __builtin_elementwise_fma(t, gelu_f32x2{ADVGRPO_GELU_C2, ADVGRPO_GELU_C2}, gelu_f32x2{ADVGRPO_GELU_C1, ADVGRPO_GELU_C1});
+    f32x2 t = x * x;
+    t = __builtin_elementwise_fma(t, f32x2{ADVGRPO_GELU_C2, ADVGRPO_GELU_C2}, f32x2{ADVGRPO_GELU_C1, ADVGRPO_GELU_C1});
     t = t * x;
-    gelu_f32x2 d = gelu_f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)} + 1.0f;
-    return x * gelu_f32x2{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+    f32x2 d = f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)} + 1.0f;
+    return x * f32x2{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
 }
 
 // d/du gelu_tanh(u), from the same sigmoid r = 1 / (1 + 2^(u (C1 + C2 u^2))) = (1 + tanh z) / 2 the forward uses:
@@ -54,11 +50,11 @@ __device__ __forceinline__ float dgelu_tanh_f32(float u) {
     return __builtin_fmaf(q, r, r);
 }
 // y[k] *= gelu'(z[k]) on four column pairs, stage by stage (see gelu_tanh_pk4)
-__device__ __forceinline__ void dgelu_tanh_mul_pk4(gelu_f32x2 (&y)[4], const gelu_f32x2 (&z)[4]) {
+__device__ __forceinline__ void dgelu_tanh_mul_pk4(f32x2 (&y)[4], const f32x2 (&z)[4]) {
 #pragma clang fp contract(off)
-    gelu_f32x2 u2[4], t[4], q[4];
-    const gelu_f32x2 c1{ADVGRPO_GELU_C1, ADVGRPO_GELU_C1}, c2{ADVGRPO_GELU_C2, ADVGRPO_GELU_C2};
-    const gelu_f32x2 k1{ADVGRPO_DGELU_K1, ADVGRPO_DGELU_K1}, k2{ADVGRPO_DGELU_K2, ADVGRPO_DGELU_K2};
+    f32x2 u2[4], t[4], q[4];
+    const f32x2 c1{ADVGRPO_GELU_C1, ADVGRPO_GELU_C1}, c2{ADVGRPO_GELU_C2, ADVGRPO_GELU_C2};
+    const f32x2 k1{ADVGRPO_DGELU_K1, ADVGRPO_DGELU_K1}, k2{ADVGRPO_DGELU_K2, ADVGRPO_DGELU_K2};
 #pragma unroll
     for (int k = 0; k < 4; ++k) u2[k] = z[k] * z[k];
 #pragma unroll
@@ -66,11 +62,11 @@ __device__ __forceinline__ void dgelu_tanh_mul_pk4(gelu_f32x2 (&y)[4], const gel
 #pragma unroll
     for (int k = 0; k < 4; ++k) t[k] = t[k] * z[k];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) t[k] = gelu_f32x2{__builtin_amdgcn_exp2f(t[k].x), __builtin_amdgcn_exp2f(t[k].y)};
+    for (int k = 0; k < 4; ++k) t[k] = f32x2{__builtin_amdgcn_exp2f(t[k].x), __builtin_amdgcn_exp2f(t[k].y)};
 #pragma unroll
     for (int k = 0; k < 4; ++k) t[k] = t[k] + 1.0f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) t[k] = gelu_f32x2{__builtin_amdgcn_rcpf(t[k].x), __builtin_amdgcn_rcpf(t[k].y)};   // r
+    for (int k = 0; k < 4; ++k) t[k] = f32x2{__builtin_amdgcn_rcpf(t[k].x), __builtin_amdgcn_rcpf(t[k].y)};   // r
 #pragma unroll
     for (int k = 0; k < 4; ++k) q[k] = __builtin_elementwise_fma(u2[k], k2, k1);
 #pragma unroll
@@ -87,21 +83,21 @@ __device__ __forceinline__ void dgelu_tanh_mul_pk4(gelu_f32x2 (&y)[4], const gel
 // operands were produced four instructions earlier.  Chain by chain (one pair after the other through one temporary) the
 // compiler had to put an s_nop between every two dependent packed operations: 333 of the 2311 instructions of the
 // bias + GELU epilogue of a tile were s_nop.
-__device__ __forceinline__ void gelu_tanh_pk4(gelu_f32x2 (&v)[4]) {
+__device__ __forceinline__ void gelu_tanh_pk4(f32x2 (&v)[4]) {
 #pragma clang fp contract(off)
-    gelu_f32x2 t[4];
+    f32x2 t[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) t[k] = v[k] * v[k];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) t[k] = __builtin_elementwise_fma(t[k], gelu_f32x2{ADVGRPO_GELU_C2, ADVGRPO_GELU_C2}, gelu_f32x2{ADVGRPO_GELU_C1, ADVGRPO_GELU_C1});
+    for (int k = 0; k < 4; ++k) t[k] = __builtin_elementwise_fma(t[k], f32x2{ADVGRPO_GELU_C2, ADVGRPO_GELU_C2}, f32x2{ADVGRPO_GELU_C1, ADVGRPO_GELU_C1});
 #pragma unroll
     for (int k = 0; k < 4; ++k) t[k] = t[k] * v[k];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) t[k] = gelu_f32x2{__builtin_amdgcn_exp2f(t[k].x), __builtin_amdgcn_exp2f(t[k].y)};
+    for (int k = 0; k < 4; ++k) t[k] = f32x2{__builtin_amdgcn_exp2f(t[k].x), __builtin_amdgcn_exp2f(t[k].y)};
 #pragma unroll
     for (int k = 0; k < 4; ++k) t[k] = t[k] + 1.0f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) t[k] = gelu_f32x2{__builtin_amdgcn_rcpf(t[k].x), __builtin_amdgcn_rcpf(t[k].y)};
+    for (int k = 0; k < 4; ++k) t[k] = f32x2{__builtin_amdgcn_rcpf(t[k].x), __builtin_amdgcn_rcpf(t[k].y)};
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = v[k] * t[k];
 }
@@ -122,17 +118,6 @@ __device__ inline float dact_fn(float u, int act) {
     // exact GELU: Phi(u) + u phi(u)
     return 0.5f * (1.0f + erff(u * 0.7071067811865476f)) + u * 0.3989422804014327f * __expf(-0.5f * u * u);
 }
-
-// compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(<N-1>)
-template <class F, int... Is>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
-    (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 
 // Grouped tile order inside an XCD's contiguous id range: ids walk down group_m (4, measured best of 1..16) row-tiles before moving to the next
 // column-tile, so the ~32-64 tiles an XCD runs at once form a near-square patch of C and share their A / W panels
@@ -165,20 +150,6 @@ __device__ __forceinline__ void gemm_epilogue_rows(const GemmParams& p, f32x4 (&
     static_assert(RPP >= 1 && LPR >= 1 && TN % 8 == 0, "wave tile too wide for the row epilogue");
     const int mrow = lane & 15, ncol = (lane >> 4) * 4;
     const int orow_l = lane / LPR, c8 = (lane % LPR) * 8;
-    auto unpack8 = [](const uint4& q, float (&f)[8]) __attribute__((always_inline)) {
-        f[0] = bf2f((bf16_t)(q.x & 0xffffu)); f[1] = bf2f((bf16_t)(q.x >> 16));
-        f[2] = bf2f((bf16_t)(q.y & 0xffffu)); f[3] = bf2f((bf16_t)(q.y >> 16));
-        f[4] = bf2f((bf16_t)(q.z & 0xffffu)); f[5] = bf2f((bf16_t)(q.z >> 16));
-        f[6] = bf2f((bf16_t)(q.w & 0xffffu)); f[7] = bf2f((bf16_t)(q.w >> 16));
-    };
-    auto pack8 = [](const float (&v)[8]) __attribute__((always_inline)) {
-        uint4 pk;
-        pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-        pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-        pk.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16);
-        pk.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
-        return pk;
-    };
     const int n = n0 + wn * TN + c8;
     float bias8[8];
     if (p.bias && n < p.N) unpack8(*reinterpret_cast<const uint4*>(p.bias + n), bias8);
@@ -194,11 +165,7 @@ __device__ __forceinline__ void gemm_epilogue_rows(const GemmParams& p, f32x4 (&
             const int m = m0 + wm * TM + i * 16 + row;
             res_q[i][ps] = uint4{0u, 0u, 0u, 0u};
             if (!p.residual || (64 % LPR != 0 && lane >= LPR * RPP) || (16 % RPP != 0 && row >= 16) || m >= p.M || n >= p.N) continue;
-            int64_t orow = m;
-            if (p.seg_rows > 0) {
-                const int bidx = m / p.seg_rows;
-                orow = (int64_t)bidx * p.seg_stride + p.seg_off + (m - bidx * p.seg_rows);
-            }
+            const int64_t orow = seg_row(m, p.seg_rows, p.seg_stride, p.seg_off);
             res_q[i][ps] = *reinterpret_cast<const uint4*>(p.residual + (int64_t)bz * p.strideR + orow * p.ldr + n);
         }
     });
@@ -215,11 +182,7 @@ __device__ __forceinline__ void gemm_epilogue_rows(const GemmParams& p, f32x4 (&
             const f32x4 hi = *reinterpret_cast<const f32x4*>(scratch + row * RS + c8 * 4 + 16);
             const int m = m0 + wm * TM + i * 16 + row;
             if (m >= p.M || n >= p.N) continue;
-            int64_t orow = m;
-            if (p.seg_rows > 0) {
-                const int bidx = m / p.seg_rows;
-                orow = (int64_t)bidx * p.seg_stride + p.seg_off + (m - bidx * p.seg_rows);
-            }
+            const int64_t orow = seg_row(m, p.seg_rows, p.seg_stride, p.seg_off);
             float v[8] = {lo[0] * p.alpha, lo[1] * p.alpha, lo[2] * p.alpha, lo[3] * p.alpha,
                           hi[0] * p.alpha, hi[1] * p.alpha, hi[2] * p.alpha, hi[3] * p.alpha};
             if (p.bias) {
@@ -305,11 +268,7 @@ __device__ __forceinline__ void gemm_epilogue_frag(const GemmParams& p, f32x4 (&
         const int m = m0 + wm * TM + i * 16 + mrow;
         const int n = n0 + wn * TN + j * 16 + ncol;
         if (m >= p.M || n >= p.N) return;
-        int64_t orow = m;
-        if (p.seg_rows > 0) {
-            const int bidx = m / p.seg_rows;
-            orow = (int64_t)bidx * p.seg_stride + p.seg_off + (m - bidx * p.seg_rows);
-        }
+        const int64_t orow = seg_row(m, p.seg_rows, p.seg_stride, p.seg_off);
         const int gb = p.gate_rows > 0 ? m / p.gate_rows : 0;
         const bf16_t* grow = p.gate ? p.gate + (int64_t)bz * p.gate_batch_stride + (int64_t)gb * p.gate_stride : nullptr;
         const bf16_t* rrow = p.residual ? p.residual + (int64_t)bz * p.strideR + orow * p.ldr : nullptr;

@@ -23,12 +23,6 @@
 
 namespace advgrpo {
 
-typedef __attribute__((ext_vector_type(4))) float tn_f32x4;
-typedef __attribute__((ext_vector_type(4))) short tn_s16x4;
-typedef __attribute__((ext_vector_type(8))) short tn_s16x8;
-typedef __attribute__((address_space(3))) void* tn_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* tn_gptr_t;
-
 struct TnParams {
     const bf16_t* P; int64_t ldp; int p_seg_rows; int64_t p_seg_stride, p_seg_off;
     const bf16_t* Q; int64_t ldq; int q_seg_rows; int64_t q_seg_stride, q_seg_off;
@@ -36,7 +30,7 @@ struct TnParams {
     int M, N1; int chunks_per_block;                // 64-token chunks per grid.y slice
 };
 
-// row of token m through the (seg_rows, seg_stride, seg_off) map of the GEMM family
+// seg_row (device_prims.hpp) with an early return: with the shared spelling both kernels of this file allocate their registers differently
 __device__ __forceinline__ int64_t tn_row(int m, int seg_rows, int64_t seg_stride, int64_t seg_off) {
     if (seg_rows <= 0) return m;
     const int b = m / seg_rows;
@@ -96,7 +90,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnParams p) {
                 const int m = min(chunk * MC + (wave + i * 4) * 4 + (lane >> 4), p.M - 1);
                 src = p.P + n1_0 + (lane & 15) * 8 + tn_row(m, p.p_seg_rows, p.p_seg_stride, p.p_seg_off) * p.ldp;
             }
-            __builtin_amdgcn_global_load_lds((tn_gptr_t)src, (tn_lds_ptr_t)(base + (wave + i * 4) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lds_ptr_t)(base + (wave + i * 4) * 1024), 16, 0, 0);
             pc[i].advance(p.ldp, p.p_seg_rows, p.p_seg_stride);
         }
 #pragma unroll
@@ -106,16 +100,16 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnParams p) {
                 const int m = min(chunk * MC + (wave + i * 4) * 8 + (lane >> 3), p.M - 1);
                 src = p.Q + (lane & 7) * 8 + tn_row(m, p.q_seg_rows, p.q_seg_stride, p.q_seg_off) * p.ldq;
             }
-            __builtin_amdgcn_global_load_lds((tn_gptr_t)src, (tn_lds_ptr_t)(base + P_BYTES + (wave + i * 4) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lds_ptr_t)(base + P_BYTES + (wave + i * 4) * 1024), 16, 0, 0);
             qc[i].advance(p.ldq, p.q_seg_rows, p.q_seg_stride);
         }
     };
 
-    tn_f32x4 acc[2][4];
+    f32x4 acc[2][4];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = tn_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // transposed fragment reads: inside a 16-lane group, lane t supplies the address of 4 contiguous features of token
     // (g*4 + t/4) and receives feature t of tokens g*4 .. g*4+3; a second read 16 tokens further completes the 8
@@ -128,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnParams p) {
     if (nch > 1) stage(1, chunk0 + 1);
     int slot = 0;
     for (int c = 0; c < nch; ++c) {
-        if (c + 1 < nch) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
+        if (c + 1 < nch) wait_vm<LOADS>();
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         const int fill = slot == 0 ? NS - 1 : slot - 1;      // slot of chunk c-1: free once every wave is past the barrier
@@ -144,10 +138,10 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnParams p) {
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
                 const char* a = pb + kc * 32 * 256 + p_off + nb * 32;
-                const tn_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tn_s16x4*)(a));
-                const tn_s16x4 hi =
-                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tn_s16x4*)(a + 16 * 256));
-                tn_s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
+                const s16x4 hi =
+                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * 256));
+                s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                 if (ragged) {   // tokens past M were clamped on the way in: zero their contribution (P side suffices)
                     asm volatile("; ragged chunk" ::: "memory");
                     const int mb = m0 + kc * 32 + g * 4;
@@ -162,10 +156,10 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnParams p) {
 #pragma unroll
             for (int qn = 0; qn < 4; ++qn) {
                 const char* a = qb + kc * 32 * 128 + q_off + qn * 32;
-                const tn_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tn_s16x4*)(a));
-                const tn_s16x4 hi =
-                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tn_s16x4*)(a + 16 * 128));
-                qf[qn] = __builtin_bit_cast(bf16x8_t, (tn_s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
+                const s16x4 hi =
+                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * 128));
+                qf[qn] = __builtin_bit_cast(bf16x8_t, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
             }
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
@@ -181,7 +175,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnParams p) {
         const int n1 = n1_0 + wave * 32 + nb * 16 + t;
 #pragma unroll
         for (int qn = 0; qn < 4; ++qn)
-            *reinterpret_cast<tn_f32x4*>(ws + (int64_t)n1 * 64 + qn * 16 + g * 4) = acc[nb][qn];
+            *reinterpret_cast<f32x4*>(ws + (int64_t)n1 * 64 + qn * 16 + g * 4) = acc[nb][qn];
     }
 }
 
@@ -224,27 +218,21 @@ struct TnProblem {
 struct TnGroup { TnProblem pr[TN_MAX]; int n; float* ws; int* counters; };
 
 typedef unsigned long long tn_u64;
-typedef __attribute__((ext_vector_type(2))) float tn_f32x2;
-__device__ __forceinline__ void tn_st16_sc1(float* p, const tn_f32x4& v) {
+__device__ __forceinline__ void tn_st16_sc1(float* p, const f32x4& v) {
     tn_u64* q = reinterpret_cast<tn_u64*>(p);
-    const tn_f32x2 lo{v[0], v[1]}, hi{v[2], v[3]};
+    const f32x2 lo{v[0], v[1]}, hi{v[2], v[3]};
     __hip_atomic_store(q, __builtin_bit_cast(tn_u64, lo), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(q + 1, __builtin_bit_cast(tn_u64, hi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ tn_f32x4 tn_ld16_sc1(const float* p) {
+__device__ __forceinline__ f32x4 tn_ld16_sc1(const float* p) {
     tn_u64* q = reinterpret_cast<tn_u64*>(const_cast<float*>(p));
-    const tn_f32x2 lo = __builtin_bit_cast(tn_f32x2, __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    const tn_f32x2 hi = __builtin_bit_cast(tn_f32x2, __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    return tn_f32x4{lo[0], lo[1], hi[0], hi[1]};
+    const f32x2 lo = __builtin_bit_cast(f32x2, __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const f32x2 hi = __builtin_bit_cast(f32x2, __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    return f32x4{lo[0], lo[1], hi[0], hi[1]};
 }
 
-// One DMA instruction of the grouped kernel: 64 lanes x 16 bytes from (uniform base + per-lane 32-bit byte offset) to LDS [lds, lds + 1 KiB).
-// Hand-written (as in attention.hpp / gemm8p_kernel.hpp): issued through the builtin, the compiler treats the DMA as a possible alias of
-// every later LDS read and waits with vmcnt(0) in front of the first fragment read of the SAME iteration -- the ring then hides nothing
-// (the per-adapter kernel above: 1.4 TB/s).
-__device__ __forceinline__ void tn_dma16(const void* base, uint32_t off, uint32_t lds) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(lds) : "memory");
-}
+// (the grouped kernel's DMA is the hand-written lds_dma16 of device_prims.hpp: behind the builtin's vmcnt(0) the ring hides nothing --
+// the per-adapter kernel above, which uses the builtin: 1.4 TB/s)
 // A lane's source cursor: byte offset of its token's row (+ column) from the operand base, and the token's position in its row segment.
 // Advancing by MC tokens is division-free.
 struct TnCur {
@@ -314,29 +302,29 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_grouped_kernel(const TnGroup g
         tn_cur_init(qc[i], min(m_begin + q_tok[i], M - 1), p.ldq, col, p.q_seg_rows, p.q_seg_stride, p.q_seg_off);
         q_last[i] = (uint32_t)((tn_row(M - 1, p.q_seg_rows, p.q_seg_stride, p.q_seg_off) * p.ldq + col) * 2);
     }
-    const uint32_t lds0 = (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)(smem)) + wave * 1024;
+    const uint32_t lds0 = lds_addr(smem) + wave * 1024;
     auto stage = [&](int slot, int m0) __attribute__((always_inline)) {      // stages are requested in increasing token order
         const uint32_t base = lds0 + slot * STAGE;
         const bool ragged = m0 + MC > M;                                      // (uniform; only the last stage of the matrix)
 #pragma unroll
         for (int i = 0; i < PI; ++i) {
             const uint32_t off = ragged && m0 + p_tok[i] >= M ? p_last[i] : pc[i].off;
-            tn_dma16(p.P, off, base + i * 4096);
+            lds_dma16(p.P, off, base + i * 4096);
             tn_cur_advance(pc[i], MC, p_step, p_sr, p_jump);
         }
 #pragma unroll
         for (int i = 0; i < QI; ++i) {
             const uint32_t off = ragged && m0 + q_tok[i] >= M ? q_last[i] : qc[i].off;
-            tn_dma16(p.Q, off, base + P_BYTES + i * 4096);
+            lds_dma16(p.Q, off, base + P_BYTES + i * 4096);
             tn_cur_advance(qc[i], MC, q_step, q_sr, q_jump);
         }
     };
 
-    tn_f32x4 acc[2][4 * NQB];
+    f32x4 acc[2][4 * NQB];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 4 * NQB; ++j) acc[i][j] = tn_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4 * NQB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     // transposed fragment reads: inside a 16-lane group, lane t supplies the address of 4 contiguous features of token
     // (g*4 + t/4) and receives feature t of tokens g*4 .. g*4+3; a second read 16 tokens further completes the 8
     // contraction values of the lane.  P and Q use the same token permutation, so the products pair up correctly.
@@ -348,7 +336,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_grouped_kernel(const TnGroup g
     if (nch > 1) stage(1, m_begin + MC);
     int slot = 0;
     for (int c = 0; c < nch; ++c) {
-        if (c + 1 < nch) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
+        if (c + 1 < nch) wait_vm<LOADS>();
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         const int fill = slot == 0 ? NS - 1 : slot - 1;      // slot of stage c-1: free once every wave is past the barrier
@@ -364,10 +352,10 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_grouped_kernel(const TnGroup g
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
                 const char* a = pb + kc * 32 * 256 + p_off + nb * 32;
-                const tn_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tn_s16x4*)(a));
-                const tn_s16x4 hi =
-                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tn_s16x4*)(a + 16 * 256));
-                tn_s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
+                const s16x4 hi =
+                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * 256));
+                s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                 if (ragged) {
                     asm volatile("; ragged stage" ::: "memory");
                     const int mb = m0 + kc * 32 + g * 4;
@@ -382,10 +370,10 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_grouped_kernel(const TnGroup g
 #pragma unroll
             for (int qn = 0; qn < 4 * NQB; ++qn) {
                 const char* a = qb + kc * 32 * Q_ROW + q_off + qn * 32;
-                const tn_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tn_s16x4*)(a));
-                const tn_s16x4 hi =
-                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tn_s16x4*)(a + 16 * Q_ROW));
-                const bf16x8_t qf = __builtin_bit_cast(bf16x8_t, (tn_s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
+                const s16x4 hi =
+                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * Q_ROW));
+                const bf16x8_t qf = __builtin_bit_cast(bf16x8_t, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 #pragma unroll
                 for (int nb = 0; nb < 2; ++nb) acc[nb][qn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, pf[nb], acc[nb][qn], 0, 0, 0);
             }
@@ -433,7 +421,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_grouped_kernel(const TnGroup g
                 acc[nb][qn] = tn_ld16_sc1(ws + (int64_t)(n1_0 + wave * 32 + nb * 16 + t) * NQ + qn * 16 + g * 4);
         for (int k = 1; k < p.slices; ++k) {
             const float* wk = ws + (int64_t)k * p.N1 * NQ;
-            tn_f32x4 v[2][4 * NQB];
+            f32x4 v[2][4 * NQB];
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
@@ -447,7 +435,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_grouped_kernel(const TnGroup g
     }
     // C += alpha * sum: every load of C first, then every store (written as `C[..] += ..` per element the compiler has to assume that a
     // store aliases the next load and serialises 8 - 96 memory round trips per lane: 120 of the 130 us of the 192-wide launch)
-    tn_f32x4 cur[2][4 * NQB];
+    f32x4 cur[2][4 * NQB];
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
         const int n1 = n1_0 + wave * 32 + nb * 16 + t;
@@ -459,7 +447,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_grouped_kernel(const TnGroup g
 #pragma unroll
                 for (int e = 0; e < 4; ++e) cur[nb][qn][e] = C[(int64_t)(n2 + e) * p.ldc + n1];
             } else {
-                cur[nb][qn] = *reinterpret_cast<const tn_f32x4*>(C + (int64_t)n1 * p.ldc + n2);
+                cur[nb][qn] = *reinterpret_cast<const f32x4*>(C + (int64_t)n1 * p.ldc + n2);
             }
         }
     }
@@ -468,14 +456,14 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_grouped_kernel(const TnGroup g
         const int n1 = n1_0 + wave * 32 + nb * 16 + t;
 #pragma unroll
         for (int qn = 0; qn < 4 * NQB; ++qn) {
-            const tn_f32x4 out = cur[nb][qn] + acc[nb][qn] * p.alpha;
+            const f32x4 out = cur[nb][qn] + acc[nb][qn] * p.alpha;
             float* C = p.C;
             const int n2 = (qn & 3) * 16 + g * 4;
             if (p.transpose_out) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) C[(int64_t)(n2 + e) * p.ldc + n1] = out[e];
             } else {
-                *reinterpret_cast<tn_f32x4*>(C + (int64_t)n1 * p.ldc + n2) = out;
+                *reinterpret_cast<f32x4*>(C + (int64_t)n1 * p.ldc + n2) = out;
             }
         }
     }

@@ -17,23 +17,6 @@ namespace advgrpo {
 
 constexpr int LN_MAX_CHUNKS = 8;  // 8-element chunks per lane => D <= 4096 (kernel instantiated for 4 and 8)
 
-__device__ inline void unpack8(const uint4& r, float o[8]) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        o[2 * k] = bf2f((bf16_t)(w[k] & 0xffffu));
-        o[2 * k + 1] = bf2f((bf16_t)(w[k] >> 16));
-    }
-}
-__device__ inline uint4 pack8(const float o[8]) {
-    uint4 r;
-    r.x = (uint32_t)f2bf(o[0]) | ((uint32_t)f2bf(o[1]) << 16);
-    r.y = (uint32_t)f2bf(o[2]) | ((uint32_t)f2bf(o[3]) << 16);
-    r.z = (uint32_t)f2bf(o[4]) | ((uint32_t)f2bf(o[5]) << 16);
-    r.w = (uint32_t)f2bf(o[6]) | ((uint32_t)f2bf(o[7]) << 16);
-    return r;
-}
-
 struct LnParams {
     const bf16_t* x; int64_t ldx;
     bf16_t* out0; bf16_t* out1; int64_t ldo;
@@ -200,8 +183,7 @@ __global__ __launch_bounds__(256) void rmsnorm_heads_kernel(bf16_t* __restrict__
     const int lane = threadIdx.x & 63;
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= M) return;
-    int64_t row = m;
-    if (seg_rows > 0) row = (int64_t)(m / seg_rows) * seg_stride + seg_off + (m % seg_rows);
+    const int64_t row = seg_row(m, seg_rows, seg_stride, seg_off);
     bf16_t* r = buf + row * ld + col0;
     const int sub = lane & 7;  // 8 lanes x 8 elements = one head
     for (int h0 = 0; h0 < nheads; h0 += 8) {

@@ -28,6 +28,7 @@ constexpr int SDE_BRANCH_COPIES = 8;             // sde_step_branch_kernel: copi
 
 __device__ inline void load8(const void* p, int dt, int64_t i, float o[8]) {
     if (dt == ADVGRPO_BF16) {
+        // (spelled out, not unpack8: through the shared helper sde_step_kernel<CpsStep> allocates its registers differently)
         const uint4 r = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p) + i);
         const uint32_t w[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
@@ -36,19 +37,12 @@ __device__ inline void load8(const void* p, int dt, int64_t i, float o[8]) {
             o[2 * k + 1] = bf2f((bf16_t)(w[k] >> 16));
         }
     } else {
-        const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p) + i);
-        const float4 b = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p) + i + 4);
-        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+        ld8_f32(reinterpret_cast<const float*>(p) + i, o);
     }
 }
 __device__ inline void store8(void* p, int dt, int64_t i, const float o[8]) {
     if (dt == ADVGRPO_BF16) {
-        uint4 r;
-        r.x = (uint32_t)f2bf(o[0]) | ((uint32_t)f2bf(o[1]) << 16);
-        r.y = (uint32_t)f2bf(o[2]) | ((uint32_t)f2bf(o[3]) << 16);
-        r.z = (uint32_t)f2bf(o[4]) | ((uint32_t)f2bf(o[5]) << 16);
-        r.w = (uint32_t)f2bf(o[6]) | ((uint32_t)f2bf(o[7]) << 16);
-        *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p) + i) = r;
+        *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p) + i) = pack8(o);
     } else {
         float* f = reinterpret_cast<float*>(p) + i;
         *reinterpret_cast<float4*>(f) = make_float4(o[0], o[1], o[2], o[3]);

@@ -16,23 +16,6 @@
 
 namespace advgrpo {
 
-__device__ inline void unpack8t(const uint4& r, float o[8]) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        o[2 * k] = bf2f((bf16_t)(w[k] & 0xffffu));
-        o[2 * k + 1] = bf2f((bf16_t)(w[k] >> 16));
-    }
-}
-__device__ inline uint4 pack8t(const float o[8]) {
-    uint4 r;
-    r.x = (uint32_t)f2bf(o[0]) | ((uint32_t)f2bf(o[1]) << 16);
-    r.y = (uint32_t)f2bf(o[2]) | ((uint32_t)f2bf(o[3]) << 16);
-    r.z = (uint32_t)f2bf(o[4]) | ((uint32_t)f2bf(o[5]) << 16);
-    r.w = (uint32_t)f2bf(o[6]) | ((uint32_t)f2bf(o[7]) << 16);
-    return r;
-}
-
 // ---- 64x64 tile transpose through LDS (padded to 65 to dodge bank conflicts); in [R, ldi] -> out [C, ldo]
 // input row r is read from (r / seg_rows) * seg_stride + seg_off + r % seg_rows when seg_rows > 0; output columns
 // [R, Rpad) are written as zeros (the weight-gradient GEMMs contract over a multiple of 64 tokens).
@@ -44,6 +27,7 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const bf16_t* __res
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     for (int i = ty; i < 64; i += 4) {
         const int r = r0 + i, c = c0 + tx;
+        // (spelled out, not seg_row: its m - b * seg_rows form compiles to another division sequence inside this loop)
         int64_t rr = r;
         if (seg_rows > 0) rr = (int64_t)(r / seg_rows) * seg_stride + seg_off + (r % seg_rows);
         tile[i][tx] = (r < R && c < C) ? in[rr * ldi + c] : (bf16_t)0;
@@ -80,7 +64,7 @@ __global__ __launch_bounds__(256) void layernorm_mod_bwd_kernel(const LnBwdParam
     for (int i = 0; i < MAXC; ++i) {
         const int c = lane + i * 64;
         if (c < nch) {
-            unpack8t(*reinterpret_cast<const uint4*>(p.x + (int64_t)row * p.ldx + c * 8), xv[i]);
+            unpack8(*reinterpret_cast<const uint4*>(p.x + (int64_t)row * p.ldx + c * 8), xv[i]);
 #pragma unroll
             for (int k = 0; k < 8; ++k) sum += xv[i][k];
         }
@@ -103,13 +87,13 @@ __global__ __launch_bounds__(256) void layernorm_mod_bwd_kernel(const LnBwdParam
         const int c = lane + i * 64;
         if (c < nch) {
             float d0[8], s0[8];
-            unpack8t(*reinterpret_cast<const uint4*>(p.dy0 + (int64_t)row * p.lddy + c * 8), d0);
-            if (p.scale0) unpack8t(*reinterpret_cast<const uint4*>(p.scale0 + mrow + c * 8), s0);
+            unpack8(*reinterpret_cast<const uint4*>(p.dy0 + (int64_t)row * p.lddy + c * 8), d0);
+            if (p.scale0) unpack8(*reinterpret_cast<const uint4*>(p.scale0 + mrow + c * 8), s0);
 #pragma unroll
             for (int k = 0; k < 8; ++k) gv[i][k] = d0[k] * (p.scale0 ? 1.0f + s0[k] : 1.0f);
             if (p.dy1) {
-                unpack8t(*reinterpret_cast<const uint4*>(p.dy1 + (int64_t)row * p.lddy + c * 8), d0);
-                unpack8t(*reinterpret_cast<const uint4*>(p.scale1 + mrow + c * 8), s0);
+                unpack8(*reinterpret_cast<const uint4*>(p.dy1 + (int64_t)row * p.lddy + c * 8), d0);
+                unpack8(*reinterpret_cast<const uint4*>(p.scale1 + mrow + c * 8), s0);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) gv[i][k] += d0[k] * (1.0f + s0[k]);
             }
@@ -127,24 +111,24 @@ __global__ __launch_bounds__(256) void layernorm_mod_bwd_kernel(const LnBwdParam
         const int c = lane + i * 64;
         if (c < nch) {
             float o[8], r[8];
-            if (p.dres) unpack8t(*reinterpret_cast<const uint4*>(p.dres + (int64_t)row * p.lddx + c * 8), r);
+            if (p.dres) unpack8(*reinterpret_cast<const uint4*>(p.dres + (int64_t)row * p.lddx + c * 8), r);
 #pragma unroll
             for (int k = 0; k < 8; ++k) o[k] = rstd * (gv[i][k] - mg - xv[i][k] * mgx) + (p.dres ? r[k] : 0.f);
-            const uint4 packed = pack8t(o);
+            const uint4 packed = pack8(o);
             *reinterpret_cast<uint4*>(p.dx + (int64_t)row * p.lddx + c * 8) = packed;
             if (p.gate_a) {
                 const int64_t grow = (int64_t)(row / p.rows_per_batch) * p.gate_stride;
                 float a[8], g[8];
-                unpack8t(packed, o);                         // the ROUNDED gradient is what the gated branch multiplies
-                unpack8t(*reinterpret_cast<const uint4*>(p.gate_a + grow + c * 8), g);
+                unpack8(packed, o);                         // the ROUNDED gradient is what the gated branch multiplies
+                unpack8(*reinterpret_cast<const uint4*>(p.gate_a + grow + c * 8), g);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) a[k] = o[k] * g[k];
-                *reinterpret_cast<uint4*>(p.gout_a + (int64_t)row * p.D + c * 8) = pack8t(a);
+                *reinterpret_cast<uint4*>(p.gout_a + (int64_t)row * p.D + c * 8) = pack8(a);
                 if (p.gate_b) {
-                    unpack8t(*reinterpret_cast<const uint4*>(p.gate_b + grow + c * 8), g);
+                    unpack8(*reinterpret_cast<const uint4*>(p.gate_b + grow + c * 8), g);
 #pragma unroll
                     for (int k = 0; k < 8; ++k) a[k] = o[k] * g[k];
-                    *reinterpret_cast<uint4*>(p.gout_b + (int64_t)row * p.D + c * 8) = pack8t(a);
+                    *reinterpret_cast<uint4*>(p.gout_b + (int64_t)row * p.D + c * 8) = pack8(a);
                 }
             }
         }
@@ -160,17 +144,16 @@ __global__ __launch_bounds__(256) void rmsnorm_heads_bwd_kernel(bf16_t* __restri
     const int lane = threadIdx.x & 63;
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= M) return;
-    int64_t row = m;
-    if (seg_rows > 0) row = (int64_t)(m / seg_rows) * seg_stride + seg_off + (m % seg_rows);
+    const int64_t row = seg_row(m, seg_rows, seg_stride, seg_off);
     const int sub = lane & 7;
     for (int h0 = 0; h0 < nheads; h0 += 8) {
         const int hh = h0 + (lane >> 3);
         if (hh >= nheads) break;
         float d[8], yy[8], ww[8];
         bf16_t* dp = dy + row * lddy + col0 + hh * 64 + sub * 8;
-        unpack8t(*reinterpret_cast<const uint4*>(dp), d);
-        unpack8t(*reinterpret_cast<const uint4*>(y + row * ldy + col0 + hh * 64 + sub * 8), yy);
-        unpack8t(*reinterpret_cast<const uint4*>(w + (hh / heads_per_weight) * 64 + sub * 8), ww);
+        unpack8(*reinterpret_cast<const uint4*>(dp), d);
+        unpack8(*reinterpret_cast<const uint4*>(y + row * ldy + col0 + hh * 64 + sub * 8), yy);
+        unpack8(*reinterpret_cast<const uint4*>(w + (hh / heads_per_weight) * 64 + sub * 8), ww);
         float dot = 0.f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -184,7 +167,7 @@ __global__ __launch_bounds__(256) void rmsnorm_heads_bwd_kernel(bf16_t* __restri
         const float r = rs[row * nheads + hh], mdot = dot * (1.0f / 64.0f);
 #pragma unroll
         for (int k = 0; k < 8; ++k) d[k] = r * (d[k] - yy[k] * mdot);
-        *reinterpret_cast<uint4*>(dp) = pack8t(d);
+        *reinterpret_cast<uint4*>(dp) = pack8(d);
     }
 }
 
@@ -217,9 +200,9 @@ __global__ __launch_bounds__(256) void qk_norm_rope_bwd_kernel(bf16_t* __restric
         if (hh >= nheads) break;
         float d[8], yy[8], ww[8];
         bf16_t* dp = dy + (int64_t)row * lddy + col0 + hh * HD + sub * 8;
-        unpack8t(*reinterpret_cast<const uint4*>(dp), d);
-        unpack8t(*reinterpret_cast<const uint4*>(y + (int64_t)row * ldy + col0 + hh * HD + sub * 8), yy);
-        unpack8t(*reinterpret_cast<const uint4*>(w + (hh / heads_per_weight) * HD + sub * 8), ww);
+        unpack8(*reinterpret_cast<const uint4*>(dp), d);
+        unpack8(*reinterpret_cast<const uint4*>(y + (int64_t)row * ldy + col0 + hh * HD + sub * 8), yy);
+        unpack8(*reinterpret_cast<const uint4*>(w + (hh / heads_per_weight) * HD + sub * 8), ww);
         float dot = 0.f;
 #pragma unroll
         for (int k = 0; k < 8; k += 2) {
@@ -235,7 +218,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_bwd_kernel(bf16_t* __restric
         const float r = rs[(int64_t)row * nheads + hh], mdot = dot * (1.0f / HD);
 #pragma unroll
         for (int k = 0; k < 8; ++k) d[k] = r * (d[k] - yy[k] * mdot);
-        *reinterpret_cast<uint4*>(dp) = pack8t(d);
+        *reinterpret_cast<uint4*>(dp) = pack8(d);
     }
 }
 
@@ -247,11 +230,11 @@ __global__ __launch_bounds__(256) void gate_mul_kernel(const bf16_t* __restrict_
         const int c = i % D8;
         const int64_t m = i / D8;
         float a[8], g[8];
-        unpack8t(*reinterpret_cast<const uint4*>(x + i * 8), a);
-        unpack8t(*reinterpret_cast<const uint4*>(gate + (m / rows_per_batch) * gate_stride + c * 8), g);
+        unpack8(*reinterpret_cast<const uint4*>(x + i * 8), a);
+        unpack8(*reinterpret_cast<const uint4*>(gate + (m / rows_per_batch) * gate_stride + c * 8), g);
 #pragma unroll
         for (int k = 0; k < 8; ++k) a[k] *= g[k];
-        *reinterpret_cast<uint4*>(y + i * 8) = pack8t(a);
+        *reinterpret_cast<uint4*>(y + i * 8) = pack8(a);
     }
 }
 

@@ -15,23 +15,6 @@
 
 namespace advgrpo {
 
-__device__ inline void unpack8v(const uint4& r, float o[8]) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        o[2 * k] = bf2f((bf16_t)(w[k] & 0xffffu));
-        o[2 * k + 1] = bf2f((bf16_t)(w[k] >> 16));
-    }
-}
-__device__ inline uint4 pack8v(const float o[8]) {
-    uint4 r;
-    r.x = (uint32_t)f2bf(o[0]) | ((uint32_t)f2bf(o[1]) << 16);
-    r.y = (uint32_t)f2bf(o[2]) | ((uint32_t)f2bf(o[3]) << 16);
-    r.z = (uint32_t)f2bf(o[4]) | ((uint32_t)f2bf(o[5]) << 16);
-    r.w = (uint32_t)f2bf(o[6]) | ((uint32_t)f2bf(o[7]) << 16);
-    return r;
-}
-
 // x: [B, HW, C] bf16.  grid (chunks, B); each block walks pixels [chunk*ppb, (chunk+1)*ppb).
 // A thread owns one 8-channel slice (c8 = tid % (C/8)) => with C/G in {4, 8, 16} its 8 channels
 // belong to at most two groups... we keep per-thread sums per 4-channel half and reduce in LDS.
@@ -39,10 +22,9 @@ __device__ inline uint4 pack8v(const float o[8]) {
 template <typename T>
 __device__ inline void load8(const T* __restrict__ q, float o[8]) {
     if constexpr (sizeof(T) == 2) {
-        unpack8v(*reinterpret_cast<const uint4*>(q), o);
+        unpack8(*reinterpret_cast<const uint4*>(q), o);
     } else {
-        const float4 a = *reinterpret_cast<const float4*>(q), b = *reinterpret_cast<const float4*>(q + 4);
-        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+        ld8_f32(q, o);
     }
 }
 // split-bf16 ("bf16x3") representation of an f32 value: hi = bf16(v), lo = bf16(v - hi) (the subtraction is exact);
@@ -56,8 +38,8 @@ __device__ inline void split8(const float v[8], uint4& hi, uint4& lo) {
         h[k] = round_bf16(v[k]);
         l[k] = v[k] - h[k];
     }
-    hi = pack8v(h);
-    lo = pack8v(l);
+    hi = pack8(h);
+    lo = pack8(l);
 }
 
 // fp16 pair ("f16x2", conv_x3.hip F16): hi = f16(s v), lo = f16(s v - hi) with a power-of-two pre-scale s that keeps un-normalised
@@ -269,7 +251,7 @@ __global__ __launch_bounds__(256) void groupnorm_apply_kernel(const T* __restric
             }
         }
         if constexpr (sizeof(T) == 2) {
-            *reinterpret_cast<uint4*>(y + i * 8) = pack8v(v);
+            *reinterpret_cast<uint4*>(y + i * 8) = pack8(v);
         } else {
             uint4 hi, lo;
             if (pair_only == 2) split8_f16(v, prescale, hi, lo);     // fp16 pair [hi | unwritten | lo]
@@ -392,7 +374,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(bf16_t* __restrict__ 
     for (int i = 0; i < MAXC; ++i) {
         const int c = i * 64 + lane;
         if (c < n8) {
-            unpack8v(*reinterpret_cast<const uint4*>(r + c * 8), v[i]);
+            unpack8(*reinterpret_cast<const uint4*>(r + c * 8), v[i]);
 #pragma unroll
             for (int k = 0; k < 8; ++k) mx = fmaxf(mx, v[i][k]);
         }
@@ -417,7 +399,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(bf16_t* __restrict__ 
         if (c < n8) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) v[i][k] *= inv;
-            *reinterpret_cast<uint4*>(r + c * 8) = pack8v(v[i]);
+            *reinterpret_cast<uint4*>(r + c * 8) = pack8(v[i]);
         }
     }
 }
@@ -607,7 +589,7 @@ __global__ __launch_bounds__(256) void rmsnorm_pixels_kernel(const T* __restrict
             v[k] = t;
         }
         if (out_mode == 0) {
-            *reinterpret_cast<uint4*>(y + pix * C + sub * 8) = pack8v(v);
+            *reinterpret_cast<uint4*>(y + pix * C + sub * 8) = pack8(v);
         } else {
             uint4 hi, lo;
             split8(v, hi, lo);
@@ -691,7 +673,7 @@ __global__ __launch_bounds__(256) void softmax_rows_long_kernel(bf16_t* __restri
     float mx = -INFINITY;
     for (int c = threadIdx.x; c < n8; c += 256) {
         float v[8];
-        unpack8v(*reinterpret_cast<const uint4*>(r + c * 8), v);
+        unpack8(*reinterpret_cast<const uint4*>(r + c * 8), v);
 #pragma unroll
         for (int k = 0; k < 8; ++k) mx = fmaxf(mx, v[k]);
     }
@@ -702,17 +684,17 @@ __global__ __launch_bounds__(256) void softmax_rows_long_kernel(bf16_t* __restri
     float sum = 0.f;
     for (int c = threadIdx.x; c < n8; c += 256) {
         float v[8];
-        unpack8v(*reinterpret_cast<const uint4*>(r + c * 8), v);
+        unpack8(*reinterpret_cast<const uint4*>(r + c * 8), v);
 #pragma unroll
         for (int k = 0; k < 8; ++k) sum += __expf(v[k] - mx);
     }
     const float inv = 1.0f / block_sum<4>(sum, red);
     for (int c = threadIdx.x; c < n8; c += 256) {
         float v[8];
-        unpack8v(*reinterpret_cast<const uint4*>(r + c * 8), v);
+        unpack8(*reinterpret_cast<const uint4*>(r + c * 8), v);
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = __expf(v[k] - mx) * inv;
-        *reinterpret_cast<uint4*>(r + c * 8) = pack8v(v);
+        *reinterpret_cast<uint4*>(r + c * 8) = pack8(v);
     }
 }
 

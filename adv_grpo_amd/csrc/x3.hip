@@ -11,18 +11,6 @@
 namespace advgrpo {
 namespace {
 
-__device__ __forceinline__ void x3_ld8(const float* q, float o[8]) {
-    const float4 a = *reinterpret_cast<const float4*>(q), b = *reinterpret_cast<const float4*>(q + 4);
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-}
-__device__ __forceinline__ uint4 x3_pack8(const float o[8]) {
-    uint4 r;
-    r.x = (uint32_t)f2bf(o[0]) | ((uint32_t)f2bf(o[1]) << 16);
-    r.y = (uint32_t)f2bf(o[2]) | ((uint32_t)f2bf(o[3]) << 16);
-    r.z = (uint32_t)f2bf(o[4]) | ((uint32_t)f2bf(o[5]) << 16);
-    r.w = (uint32_t)f2bf(o[6]) | ((uint32_t)f2bf(o[7]) << 16);
-    return r;
-}
 // row + c*8 of the three K thirds
 __device__ __forceinline__ void x3_store(bf16_t* row, int K, int c8, const float v[8], int order) {
     float h[8], l[8];
@@ -31,7 +19,7 @@ __device__ __forceinline__ void x3_store(bf16_t* row, int K, int c8, const float
         h[k] = round_bf16(v[k]);
         l[k] = v[k] - h[k];               // exact
     }
-    const uint4 hi = x3_pack8(h), lo = x3_pack8(l);
+    const uint4 hi = pack8(h), lo = pack8(l);
     *reinterpret_cast<uint4*>(row + c8) = hi;
     *reinterpret_cast<uint4*>(row + K + c8) = order ? lo : hi;
     *reinterpret_cast<uint4*>(row + 2 * K + c8) = order ? hi : lo;
@@ -53,7 +41,7 @@ __global__ __launch_bounds__(256) void layernorm_x3_kernel(const float* __restri
     for (int i = 0; i < X3_LN_CHUNKS; ++i) {
         const int c = lane + i * 64;
         if (c < nch) {
-            x3_ld8(xr + c * 8, v[i]);
+            ld8_f32(xr + c * 8, v[i]);
 #pragma unroll
             for (int k = 0; k < 8; ++k) sum += v[i][k];
         }
@@ -78,8 +66,8 @@ __global__ __launch_bounds__(256) void layernorm_x3_kernel(const float* __restri
         const int c = lane + i * 64;
         if (c >= nch) continue;
         float ww[8], bb[8], o[8];
-        x3_ld8(w + c * 8, ww);
-        x3_ld8(b + c * 8, bb);
+        ld8_f32(w + c * 8, ww);
+        ld8_f32(b + c * 8, bb);
 #pragma unroll
         for (int k = 0; k < 8; ++k) o[k] = (v[i][k] - mean) * rstd * ww[k] + bb[k];
         x3_store(orow, D, c * 8, o, 0);
@@ -98,10 +86,10 @@ __global__ __launch_bounds__(256) void split_act_x3_kernel(const float* __restri
         const int slice = i % k8n;
         const int64_t r = i / k8n;
         float v[8];
-        x3_ld8(x + i * 8, v);
+        ld8_f32(x + i * 8, v);
         if (bias) {
             float b8[8];
-            x3_ld8(bias + slice * 8, b8);
+            ld8_f32(bias + slice * 8, b8);
 #pragma unroll
             for (int k = 0; k < 8; ++k) v[k] += b8[k];
         }
@@ -124,7 +112,7 @@ __global__ __launch_bounds__(256) void softmax_x3_masked_kernel(const float* __r
     float mx = -INFINITY;
     for (int c = threadIdx.x; c < n8; c += 256) {
         float v[8];
-        x3_ld8(r + c * 8, v);
+        ld8_f32(r + c * 8, v);
 #pragma unroll
         for (int k = 0; k < 8; ++k)
             if (c * 8 + k < valid) mx = fmaxf(mx, v[k] * alpha);
@@ -137,7 +125,7 @@ __global__ __launch_bounds__(256) void softmax_x3_masked_kernel(const float* __r
     float sum = 0.f;
     for (int c = threadIdx.x; c < n8; c += 256) {
         float v[8];
-        x3_ld8(r + c * 8, v);
+        ld8_f32(r + c * 8, v);
 #pragma unroll
         for (int k = 0; k < 8; ++k)
             if (c * 8 + k < valid) sum += expf(v[k] * alpha - mx);
@@ -145,7 +133,7 @@ __global__ __launch_bounds__(256) void softmax_x3_masked_kernel(const float* __r
     const float inv = 1.0f / block_sum<4>(sum, red);
     for (int c = threadIdx.x; c < n8; c += 256) {
         float v[8];
-        x3_ld8(r + c * 8, v);
+        ld8_f32(r + c * 8, v);
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = c * 8 + k < valid ? expf(v[k] * alpha - mx) * inv : 0.f;
         x3_store(o, n, c * 8, v, 0);
