@@ -5,20 +5,12 @@
 // via diffusers' JointAttnProcessor2_0 -> F.scaled_dot_product_attention) and the ViT reward
 // towers (DINOv2-B 1370 tokens, 12 heads x 64; CLIP text 77 tokens causal).
 //
-// CDNA4 mapping (wave64, v_mfma_f32_16x16x32_bf16):
-//   * workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 queries.
-//   * S^T = K Q^T is computed with K as the MFMA A operand, so a lane holds scores of ONE query
-//     (column lane&15) for 16 keys: row max / row sum are in-lane plus two cross-lane steps, and
-//     the probabilities are already in the B-operand layout of the P V product -- no LDS round
-//     trip and no permutes between the two MFMAs (the key order inside a 32-deep MFMA step is
-//     permuted consistently on the P and the V side, which a sum over keys does not see).
-//   * V^T fragments come from the row-major V tile through ds_read_b64_tr_b16 (hardware
-//     transpose), K fragments through ds_read_b128; both tiles use a 144-byte row pitch, which
-//     spreads the 16 rows of a fragment over all 16-byte bank slots.
-//   * K/V tiles are register staged: the next tile's global loads are issued before the current
-//     tile's MFMAs and written to the other LDS buffer afterwards (one barrier per tile).
-//   * O is kept transposed in the accumulators (lane = one query, 4 consecutive d): the online
-//     softmax rescale is a per-lane scalar and the epilogue is an 8-byte bf16x4 store per lane.
+// Mapping of attention_fwd_kernel (the fragment layouts and the tile step -- mask, online softmax, P V, epilogue -- are attention.hpp's):
+//   * workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 queries (two blocks of 16).
+//   * K fragments come from LDS through ds_read_b128, V^T fragments through ds_read_b64_tr_b16; both tiles use a 144-byte row
+//     pitch, which spreads the 16 rows of a fragment over all 16-byte bank slots.
+//   * K/V tiles are register staged: the next tile's global loads are issued before the current tile's MFMAs and written to the
+//     other LDS buffer afterwards (one barrier per tile).
 #include <stdlib.h>
 
 #include "attention.hpp"
@@ -149,100 +141,15 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttnParams p) 
         }
         // lane holds S[key = kv0 + kb*16 + g*4 + r][query = q0 + qb*16 + t]
         const bool edge = (kv0 + ATT_KB > p.Skv) || p.causal;
-        if (edge) {
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                for (int qb = 0; qb < 2; ++qb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int key = kv0 + kb * 16 + g * 4 + r;
-                        const int qi = q0 + qb * 16 + t;
-                        if (key >= p.Skv || (p.causal && key > qi)) s[kb][qb][r] = -INFINITY;
-                    }
-        }
-        // ---- online softmax (base-2), per query block
+        if (edge) ADVGRPO_MASK_SCORES(s, 2, kv0, q0, p.Skv, p.causal, g, t);
         bf16x8_t pf[2][2];  // [qb][key pair]
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb) {
-            float mx = -INFINITY;
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[kb][qb][r]);
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run[qb], mx * p.scale_log2e);
-            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;  // fully masked so far
-            const float alpha = __builtin_amdgcn_exp2f(m_run[qb] - m_use);
-            m_run[qb] = m_new;
-            float psum = 0.f;
-            float pv[4][4];
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float e = __builtin_amdgcn_exp2f(s[kb][qb][r] * p.scale_log2e - m_use);
-                    pv[kb][r] = e;
-                    psum += e;
-                }
-            l_run[qb] = l_run[qb] * alpha + psum;
-#pragma unroll
-            for (int db = 0; db < DB; ++db) o[db][qb] *= alpha;
-#pragma unroll
-            for (int kpair = 0; kpair < 2; ++kpair) {
-                bf16x8_t f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    f[r] = (__bf16)pv[2 * kpair][r];
-                    f[4 + r] = (__bf16)pv[2 * kpair + 1][r];
-                }
-                pf[qb][kpair] = f;
-            }
-        }
-        // ---- O^T[d][q] += V^T P^T ; A operand = V^T via transpose reads
-#pragma unroll
-        for (int kpair = 0; kpair < 2; ++kpair) {
-#pragma unroll
-            for (int db = 0; db < DB; ++db) {
-                const bf16_t* a0 = Vt + ((2 * kpair) * 16 + g * 4 + (t >> 2)) * ATT_PITCH + db * 16 + (t & 3) * 4;
-                const bf16_t* a1 = a0 + 16 * ATT_PITCH;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) s16x4*)(a0));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) s16x4*)(a1));
-                const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                const bf16x8_t vf = __builtin_bit_cast(bf16x8_t, both);
-#pragma unroll
-                for (int qb = 0; qb < 2; ++qb)
-                    o[db][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qb][kpair], o[db][qb], 0, 0, 0);
-            }
-        }
+        ADVGRPO_SOFTMAX_TILE(s, 2, DB, m_run, l_run, o, p.scale_log2e, pf);
+        ADVGRPO_PV_TILE(Vt, ATT_PITCH, 2, DB, pf, o, 4, g, t);
         if (it + 1 < nt) commit(buf ^ 1);
         __syncthreads();
     }
 
-    // ---- epilogue: normalise and store bf16x4 (query t, d = db*16 + g*4 .. +3)
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-        float l = l_run[qb];
-        l += __shfl_xor(l, 16, 64);
-        l += __shfl_xor(l, 32, 64);
-        const float inv = l > 0.f ? 1.0f / l : 0.f;
-        const int qi = q0 + qb * 16 + t;
-        if (qi >= p.Sq) continue;
-        if (p.lse && g == 0) p.lse[((int64_t)b * p.H + h) * p.Sq + qi] = m_run[qb] + __builtin_amdgcn_logf(l);
-        bf16_t* op = p.o + (int64_t)b * p.bso + (int64_t)qi * p.ldo + h * HD + g * 4;
-#pragma unroll
-        for (int db = 0; db < DB; ++db) {
-            if (db * 16 + g * 4 >= HD) continue;     // HD = 72: lanes g >= 2 of the last block hold padding columns
-            const f32x4 v = o[db][qb] * inv;
-            uint2 pk;
-            pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-            pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-            *reinterpret_cast<uint2*>(op + db * 16) = pk;
-        }
-    }
+    ADVGRPO_STORE_ROWS(HD, 2, DB, o, l_run, m_run, p.o + (int64_t)b * p.bso, p.ldo, h * HD, p.lse, ((int64_t)b * p.H + h) * p.Sq, q0, p.Sq, g, t);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -258,7 +165,8 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttnParams p) 
 // (chunk c + 1, row r) -- five two-way conflicts per group, the bank-conflict share of round 5's PMC; V rows are packed at
 // 160 bytes: the 8 rows x 32 bytes a ds_read_b64_tr_b16 lane group touches tile the 256 bytes of the banks exactly
 // (0,160,64,224,128,32,192,96).
-// Same arithmetic in the same order as attention_fwd_kernel<80> (key blocks past the last key are skipped: they add zeros).
+// The tile step is attention_fwd_kernel<80>'s (attention.hpp): the same arithmetic in the same order, the same bits (key blocks past
+// the last key are skipped: they add zeros; tests/test_gpu_attention_parity.py holds the two kernels to bit equality).
 constexpr int RES_MAXT = 5;        // resident key tiles of ATT_KB rows (Skv <= 320)
 constexpr int RES_MAXC = 2;        // query chunks per wave
 constexpr int RES_WAVES = 8;       // waves per workgroup: two per SIMD, so one wave's softmax (VALU) runs beside the other's MFMAs
@@ -380,94 +288,13 @@ __global__ __launch_bounds__(RES_THREADS) void attention_fwd_resident_kernel(con
                 }
             }
             // lane holds S[key = kv0 + kb*16 + g*4 + r][query = q0 + qb*16 + t]
-            if (kv0 + ATT_KB > p.Skv) {
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                    for (int qb = 0; qb < NQB; ++qb)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (kv0 + kb * 16 + g * 4 + r >= p.Skv) s[kb][qb][r] = -INFINITY;
-            }
-            // ---- online softmax (base-2), per query block
+            if (kv0 + ATT_KB > p.Skv) ADVGRPO_MASK_SCORES(s, NQB, kv0, q0, p.Skv, false, g, t);
             bf16x8_t pf[NQB][2];  // [qb][key pair]
-#pragma unroll
-            for (int qb = 0; qb < NQB; ++qb) {
-                float mx = -INFINITY;
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[kb][qb][r]);
-                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                const float m_new = fmaxf(m_run[qb], mx * p.scale_log2e);
-                const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-                const float alpha = __builtin_amdgcn_exp2f(m_run[qb] - m_use);
-                m_run[qb] = m_new;
-                float psum = 0.f;
-                float pv[4][4];
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float e = __builtin_amdgcn_exp2f(s[kb][qb][r] * p.scale_log2e - m_use);
-                        pv[kb][r] = e;
-                        psum += e;
-                    }
-                l_run[qb] = l_run[qb] * alpha + psum;
-#pragma unroll
-                for (int db = 0; db < DB; ++db) o[db][qb] *= alpha;
-#pragma unroll
-                for (int kpair = 0; kpair < 2; ++kpair) {
-                    bf16x8_t f;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        f[r] = (__bf16)pv[2 * kpair][r];
-                        f[4 + r] = (__bf16)pv[2 * kpair + 1][r];
-                    }
-                    pf[qb][kpair] = f;
-                }
-            }
-            // ---- O^T[d][q] += V^T P^T ; A operand = V^T via transpose reads
-#pragma unroll
-            for (int kpair = 0; kpair < 2; ++kpair) {
-                if (2 * kpair < nkb) {
-#pragma unroll
-                    for (int db = 0; db < DB; ++db) {
-                        const bf16_t* a0 = Vt + ((2 * kpair) * 16 + g * 4 + (t >> 2)) * VP + db * 16 + (t & 3) * 4;
-                        const bf16_t* a1 = a0 + 16 * VP;
-                        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-                        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a1));
-                        const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                        const bf16x8_t vf = __builtin_bit_cast(bf16x8_t, both);
-#pragma unroll
-                        for (int qb = 0; qb < NQB; ++qb)
-                            o[db][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qb][kpair], o[db][qb], 0, 0, 0);
-                    }
-                }
-            }
+            ADVGRPO_SOFTMAX_TILE(s, NQB, DB, m_run, l_run, o, p.scale_log2e, pf);
+            ADVGRPO_PV_TILE(Vt, VP, NQB, DB, pf, o, nkb, g, t);
         }
 
-        // ---- epilogue: normalise and store bf16x4 (query t, d = db*16 + g*4 .. +3)
-#pragma unroll
-        for (int qb = 0; qb < NQB; ++qb) {
-            float l = l_run[qb];
-            l += __shfl_xor(l, 16, 64);
-            l += __shfl_xor(l, 32, 64);
-            const float inv = l > 0.f ? 1.0f / l : 0.f;
-            const int qi = q0 + qb * 16 + t;
-            if (qi >= p.Sq) continue;
-            if (p.lse && g == 0) p.lse[((int64_t)b * p.H + h) * p.Sq + qi] = m_run[qb] + __builtin_amdgcn_logf(l);
-            bf16_t* op = p.o + (int64_t)b * p.bso + (int64_t)qi * p.ldo + h * HD + g * 4;
-#pragma unroll
-            for (int db = 0; db < DB; ++db) {
-                const f32x4 v = o[db][qb] * inv;
-                uint2 pk;
-                pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-                pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-                *reinterpret_cast<uint2*>(op + db * 16) = pk;
-            }
-        }
+        ADVGRPO_STORE_ROWS(HD, NQB, DB, o, l_run, m_run, p.o + (int64_t)b * p.bso, p.ldo, h * HD, p.lse, ((int64_t)b * p.H + h) * p.Sq, q0, p.Sq, g, t);
     }
 }
 
@@ -637,17 +464,9 @@ __global__ __launch_bounds__(256, ATT_WGS) void attention_fwd_glds_kernel(const 
         const bool edge = (kv0 + ATT_KB > p.Skv) || p.causal;
         if (edge) {   // ragged last tile / causal only: a real (wave-uniform) branch, interior tiles pay nothing
             asm volatile("; masked tile" ::: "memory");
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                for (int qb = 0; qb < 2; ++qb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int key = kv0 + kb * 16 + g * 4 + r;
-                        const int qi = q0 + qb * 16 + t;
-                        if (key >= p.Skv || (p.causal && key > qi)) s[kb][qb][r] = -INFINITY;
-                    }
+            ADVGRPO_MASK_SCORES(s, 2, kv0, q0, p.Skv, p.causal, g, t);
         }
+        // (not ADVGRPO_SOFTMAX_TILE: exp2 arguments on v_pk_fma_f32 pairs, permlane-swap lane exchanges, and a ballot that skips the rescale of O)
         bf16x8_t pf[2][2];
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
@@ -698,11 +517,7 @@ __global__ __launch_bounds__(256, ATT_WGS) void attention_fwd_glds_kernel(const 
 #pragma unroll
             for (int db = 0; db < 4; ++db) {
                 const char* a0 = Vt + (2 * kpair) * 2048 + v_base + ((db ^ v_sw) << 5);
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) s16x4*)(a0 + 2048));
-                const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                const bf16x8_t vf = __builtin_bit_cast(bf16x8_t, both);
+                const bf16x8_t vf = ld_tr_frag(a0, a0 + 2048);
 #pragma unroll
                 for (int qb = 0; qb < 2; ++qb)
                     o[db][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qb][kpair], o[db][qb], 0, 0, 0);
@@ -725,10 +540,7 @@ __global__ __launch_bounds__(256, ATT_WGS) void attention_fwd_glds_kernel(const 
 #pragma unroll
         for (int db = 0; db < 4; ++db) {
             const f32x4 v = o[db][qb] * inv;
-            uint2 pk;
-            pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-            pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-            *reinterpret_cast<uint2*>(ob + r * 128 + (((db * 2 + (g >> 1)) ^ (r & 7)) << 4) + (g & 1) * 8) = pk;
+            *reinterpret_cast<uint2*>(ob + r * 128 + (((db * 2 + (g >> 1)) ^ (r & 7)) << 4) + (g & 1) * 8) = pack4(v[0], v[1], v[2], v[3]);
         }
     }
 #pragma unroll
@@ -787,10 +599,9 @@ int attention_fwd(const AttnParams& p_in, int B, int head_dim, hipStream_t s) {
 
 using namespace advgrpo;
 
-extern "C" int advgrpo_attention_fwd(const void* q, const void* k, const void* v, void* o, int64_t ldq, int64_t ldk,
-                                     int64_t ldv, int64_t ldo, int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso,
-                                     int B, int H, int Sq, int Skv, int head_dim, float scale, int causal,
-                                     float* lse, void* stream) {
+// the C arguments both entries share -> AttnParams (lse / bias are the caller's; nqb, nwg, xcd_local are attention_fwd's)
+static AttnParams attn_params(const void* q, const void* k, const void* v, void* o, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                              int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso, int H, int Sq, int Skv, float scale, int causal) {
     AttnParams p{};
     p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o;
     p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
@@ -798,6 +609,14 @@ extern "C" int advgrpo_attention_fwd(const void* q, const void* k, const void* v
     p.H = H; p.Sq = Sq; p.Skv = Skv;
     p.scale_log2e = scale * 1.4426950408889634f;
     p.causal = causal;
+    return p;
+}
+
+extern "C" int advgrpo_attention_fwd(const void* q, const void* k, const void* v, void* o, int64_t ldq, int64_t ldk,
+                                     int64_t ldv, int64_t ldo, int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso,
+                                     int B, int H, int Sq, int Skv, int head_dim, float scale, int causal,
+                                     float* lse, void* stream) {
+    AttnParams p = attn_params(q, k, v, o, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, H, Sq, Skv, scale, causal);
     p.lse = lse;
     return attention_fwd(p, B, head_dim, as_stream(stream));
 }
@@ -818,13 +637,7 @@ extern "C" int advgrpo_attention_fwd_bias(const void* q, const void* k, const vo
                                           int B, int H, int Sq, int Skv, int head_dim, float scale, int causal,
                                           const float* bias, void* stream) {
     ADVGRPO_CHECK(bias, "attention_fwd_bias: null bias");
-    AttnParams p{};
-    p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o;
-    p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-    p.bsq = bsq; p.bsk = bsk; p.bsv = bsv; p.bso = bso;
-    p.H = H; p.Sq = Sq; p.Skv = Skv;
-    p.scale_log2e = scale * 1.4426950408889634f;
-    p.causal = causal;
+    AttnParams p = attn_params(q, k, v, o, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, H, Sq, Skv, scale, causal);
     p.bias = bias;
     return attention_fwd(p, B, head_dim, as_stream(stream));
 }

@@ -219,10 +219,7 @@ __global__ __launch_bounds__(BP_WAVES * 64, BP_WAVES == 4 ? 2 : 1) void attn_bwd
     };
     auto tfrag = [&](int off, int db) __attribute__((always_inline)) {
         if constexpr ((BP_ABL & 4) != 0) return bf0[db];
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + t_off[db][0] + off));
-        const s16x4 up = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(smem + t_off[db][1] + off));
-        const s16x8 both = __builtin_shufflevector(lo, up, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(bf16x8_t, both);
+        return ld_tr_frag(smem + t_off[db][0] + off, smem + t_off[db][1] + off);
     };
     // the -L/c (which = 0) or -D (1) values of the 32 streamed queries of a tile, in the accumulator's row order
     auto vec_init = [&](f32x16& dst, int voff, int which) __attribute__((always_inline)) {

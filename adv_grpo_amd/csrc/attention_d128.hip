@@ -183,10 +183,7 @@ __global__ __launch_bounds__(512, 2) void attention_fwd_d128_kernel(const std::c
     auto vfrag = [&](int imm, int db) __attribute__((always_inline)) {          // imm = slot * TILE + kk * 4096
         if constexpr ((D128_VAR & 32) != 0) return qf[db];
         const char* a0 = smem + v_off[db] + imm;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-        const s16x4 up = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 2048));
-        const s16x8 both = __builtin_shufflevector(lo, up, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(bf16x8_t, both);
+        return ld_tr_frag(a0, a0 + 2048);
     };
 
     f32x16 o[4];          // O^T accumulators: d block db, lane (query = lane & 31, hi): d = db*32 + 8*(r>>2) + 4*hi + (r&3)

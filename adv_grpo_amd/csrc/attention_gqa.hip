@@ -6,16 +6,14 @@
 // of BASELINE config 5, adv_grpo_amd/qwen_text_encoder.py): the packed q | k | v GEMM output is read in place, no head-major copies, no
 // repeat_interleave of K / V, no materialised scores -- and no 512-token cap.
 //
-// Mapping (wave64, v_mfma_f32_16x16x32_bf16; the fragment layouts are those of attention_fwd_kernel in attention.hip):
+// Mapping (wave64, v_mfma_f32_16x16x32_bf16; the fragment layouts and the tile step -- mask, online softmax, P V, epilogue -- are attention.hpp's):
 //   * a workgroup (4 waves) serves one (batch, key/value head, chunk of up to 8 query heads of the group, block of query positions) and
 //     stages each 64-key K and V tile in LDS ONCE for all of them: with 7 query heads per key/value head a K / V byte is fetched once
 //     where the materialised path made 7 copies.
 //   * the work is cut into 8 units of 32 rows (one query head x 32 positions); wave w owns units w and w + 4.  With g = min(Hq / Hkv, 8)
 //     heads in the chunk a workgroup covers 8 / g blocks of 32 positions (g = 1: 256 positions of one head, g = 7: 32 positions of 7 heads,
 //     one unit idle).
-//   * S^T = K Q^T with K as the A operand: a lane holds the scores of ONE query for 16 keys, so the row maximum / sum are in-lane plus two
-//     cross-lane steps and the probabilities are already in the B-operand layout of P V.  V^T fragments come from the row-major V tile
-//     through ds_read_b64_tr_b16.  Both tiles use a 272-byte row pitch (an odd multiple of 16 bytes).
+//   * both LDS tiles use a 272-byte row pitch (an odd multiple of 16 bytes).
 //   * ordinary online softmax: a running maximum with a rescale of O and of the row sum per tile.  No first-tile-maximum shortcut, hence
 //     no fallback path and no fallback counter.
 //   * causal: key tiles above the workgroup's last query position are never staged, a unit skips the tiles above its own last position,
@@ -163,73 +161,11 @@ __global__ __launch_bounds__(256) void attention_fwd_gqa_kernel(const GqaParams 
             }
             // lane holds S[key = kv0 + kb*16 + g*4 + r][query = q0 + qb*16 + t]
             const bool edge = (kv0 + ATT_KB > p.S) || (p.causal && kv0 + ATT_KB - 1 > q0[j]);
-            if (edge) {
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                    for (int qb = 0; qb < 2; ++qb)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int key = kv0 + kb * 16 + g * 4 + r;
-                            const int qi = q0[j] + qb * 16 + t;
-                            if (key >= p.S || (p.causal && key > qi)) s[kb][qb][r] = -INFINITY;
-                        }
-            }
-            // ---- online softmax (base 2) with a running maximum, per query block
+            if (edge) ADVGRPO_MASK_SCORES(s, 2, kv0, q0[j], p.S, p.causal, g, t);
+            // ordinary online softmax with a running maximum (no first-tile-maximum shortcut)
             bf16x8_t pf[2][2];  // [qb][key pair]
-#pragma unroll
-            for (int qb = 0; qb < 2; ++qb) {
-                float mx = -INFINITY;
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[kb][qb][r]);
-                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                const float m_new = fmaxf(m_run[j][qb], mx * p.scale_log2e);
-                const float m_use = (m_new == -INFINITY) ? 0.f : m_new;  // fully masked so far
-                const float alpha = __builtin_amdgcn_exp2f(m_run[j][qb] - m_use);
-                m_run[j][qb] = m_new;
-                float psum = 0.f;
-                float pv[4][4];
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float e = __builtin_amdgcn_exp2f(s[kb][qb][r] * p.scale_log2e - m_use);
-                        pv[kb][r] = e;
-                        psum += e;
-                    }
-                l_run[j][qb] = l_run[j][qb] * alpha + psum;
-#pragma unroll
-                for (int db = 0; db < DB; ++db) o[j][db][qb] *= alpha;
-#pragma unroll
-                for (int kpair = 0; kpair < 2; ++kpair) {
-                    bf16x8_t f;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        f[r] = (__bf16)pv[2 * kpair][r];
-                        f[4 + r] = (__bf16)pv[2 * kpair + 1][r];
-                    }
-                    pf[qb][kpair] = f;
-                }
-            }
-            // ---- O^T[d][q] += V^T P^T ; A operand = V^T via transpose reads
-#pragma unroll
-            for (int kpair = 0; kpair < 2; ++kpair) {
-#pragma unroll
-                for (int db = 0; db < DB; ++db) {
-                    const bf16_t* a0 = Vs + ((2 * kpair) * 16 + g * 4 + (t >> 2)) * PITCH + db * 16 + (t & 3) * 4;
-                    const bf16_t* a1 = a0 + 16 * PITCH;
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a1));
-                    const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                    const bf16x8_t vf = __builtin_bit_cast(bf16x8_t, both);
-#pragma unroll
-                    for (int qb = 0; qb < 2; ++qb)
-                        o[j][db][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qb][kpair], o[j][db][qb], 0, 0, 0);
-                }
-            }
+            ADVGRPO_SOFTMAX_TILE(s, 2, DB, m_run[j], l_run[j], o[j], p.scale_log2e, pf);
+            ADVGRPO_PV_TILE(Vs, PITCH, 2, DB, pf, o[j], 4, g, t);
         }
         __syncthreads();                 // every wave has read the tile
         if (it + 1 < nt) { GQA_COMMIT() }
@@ -239,28 +175,10 @@ __global__ __launch_bounds__(256) void attention_fwd_gqa_kernel(const GqaParams 
 #undef GQA_ISSUE
 #undef GQA_COMMIT
 
-    // ---- epilogue: normalise and store bf16x4 (query t, d = db*16 + g*4 .. +3)
 #pragma unroll
     for (int j = 0; j < GQA_UPW; ++j) {
         if (!active[j]) continue;
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb) {
-            float l = l_run[j][qb];
-            l += __shfl_xor(l, 16, 64);
-            l += __shfl_xor(l, 32, 64);
-            const float inv = l > 0.f ? 1.0f / l : 0.f;
-            const int qi = q0[j] + qb * 16 + t;
-            if (qi >= p.S) continue;
-            bf16_t* op = p.o + (int64_t)b * p.bso + (int64_t)qi * p.ldo + head[j] * HD + g * 4;
-#pragma unroll
-            for (int db = 0; db < DB; ++db) {
-                const f32x4 v = o[j][db][qb] * inv;
-                uint2 pk;
-                pk.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-                pk.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-                *reinterpret_cast<uint2*>(op + db * 16) = pk;
-            }
-        }
+        ADVGRPO_STORE_ROWS(HD, 2, DB, o[j], l_run[j], m_run[j], p.o + (int64_t)b * p.bso, p.ldo, head[j] * HD, (float*)nullptr, 0, q0[j], p.S, g, t);
     }
 }
 

@@ -169,10 +169,7 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_pipe_kernel(const AttnPa
     auto vfrag = [&](int off, int db) __attribute__((always_inline)) {
         if constexpr ((ATT_ABL & 4) != 0) return qf[db];
         const char* a0 = smem + v_off[db] + off;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-        const s16x4 up = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 1024));
-        const s16x8 both = __builtin_shufflevector(lo, up, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(bf16x8_t, both);
+        return ld_tr_frag(a0, a0 + 1024);
     };
 
     const int nt = (p.Skv + ATT_KB - 1) / ATT_KB;

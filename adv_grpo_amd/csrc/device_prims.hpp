@@ -1,5 +1,5 @@
-// device_prims.hpp -- the small device primitives every kernel file needs: vector / address-space types, bf16 x 8 packing,
-// the packed convert, the hand-written LDS-DMA instruction, counted waits, compile-time loops and tags, the segmented row
+// device_prims.hpp -- the small device primitives every kernel file needs: vector / address-space types, bf16 x 8 / x 4 packing,
+// the packed convert, the transpose-read MFMA operand, the hand-written LDS-DMA instruction, counted waits, compile-time loops and tags, the segmented row
 // map and the scheduling macros.  One definition each, with the reason it is written the way it is; included through
 // common.hpp (which it needs for bf2f / f2bf).  A kernel file keeps only its own experiment knobs as thin wrappers.
 #pragma once
@@ -13,6 +13,7 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4;    // one ds_read_tr16_b64
 typedef __attribute__((ext_vector_type(8))) short s16x8;    // two of them: an MFMA fragment before the bit cast
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;   // ... and after it: one bf16 MFMA A / B operand
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gptr_t;
 
@@ -53,6 +54,13 @@ __device__ __forceinline__ uint4 pack8(const float o[8]) {
     r.w = (uint32_t)f2bf(o[6]) | ((uint32_t)f2bf(o[7]) << 16);
     return r;
 }
+// four f32 -> 4 bf16 in a uint2 (the 8-byte lane store of an MFMA accumulator row)
+__device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) {
+    uint2 r;
+    r.x = (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16);
+    r.y = (uint32_t)f2bf(c) | ((uint32_t)f2bf(d) << 16);
+    return r;
+}
 // 8 consecutive f32 (two 16-byte loads)
 __device__ __forceinline__ void ld8_f32(const float* q, float o[8]) {
     const float4 a = *reinterpret_cast<const float4*>(q), b = *reinterpret_cast<const float4*>(q + 4);
@@ -72,6 +80,18 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) { return cvt
 // accumulators were not padded against the MFMAs that had just written them, and the reference maximum of the attention
 // forward came out of half-written registers)
 __device__ __forceinline__ float max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
+
+// ---- a 16 x 32 bf16 MFMA operand out of a row-major LDS tile through the hardware transpose: two ds_read_b64_tr_b16, the second
+// 16 rows further on (lo -> elements 0..3, hi -> 4..7).  ld_tr_s16x8 is the fragment before the bit cast, for a caller that
+// zeroes elements of it (the ragged chunks of gemm_tn.hip).
+__device__ __forceinline__ s16x8 ld_tr_s16x8(const void* lo_ptr, const void* hi_ptr) {
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(lo_ptr));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(hi_ptr));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+__device__ __forceinline__ bf16x8_t ld_tr_frag(const void* lo_ptr, const void* hi_ptr) {
+    return __builtin_bit_cast(bf16x8_t, ld_tr_s16x8(lo_ptr, hi_ptr));
+}
 
 // ---- LDS-DMA: one instruction, 64 lanes x 16 bytes -> LDS [lds, lds + 1 KiB), lane-linear.
 // Hand-written (m0 = the LDS address, the s_nop between the write of m0 and its use, the memory clobber), not

@@ -304,10 +304,7 @@ __device__ __forceinline__ void gemm_epilogue_frag(const GemmParams& p, f32x4 (&
                 v2 += bf2f((bf16_t)(q.y & 0xffffu)); v3 += bf2f((bf16_t)(q.y >> 16));
             }
             if (p.aux_out) {
-                uint2 pk;
-                pk.x = (uint32_t)f2bf(v0) | ((uint32_t)f2bf(v1) << 16);
-                pk.y = (uint32_t)f2bf(v2) | ((uint32_t)f2bf(v3) << 16);
-                *reinterpret_cast<uint2*>(p.aux_out + (int64_t)bz * p.strideC + orow * p.ld_aux + n) = pk;
+                *reinterpret_cast<uint2*>(p.aux_out + (int64_t)bz * p.strideC + orow * p.ld_aux + n) = pack4(v0, v1, v2, v3);
             }
             if (p.act >= ACT_DGELU_TANH) {
                 const uint2 q = *reinterpret_cast<const uint2*>(p.aux_in + (int64_t)bz * p.strideC + orow * p.ld_aux + n);
@@ -327,10 +324,7 @@ __device__ __forceinline__ void gemm_epilogue_frag(const GemmParams& p, f32x4 (&
                 v2 += bf2f((bf16_t)(q.y & 0xffffu)); v3 += bf2f((bf16_t)(q.y >> 16));
             }
             if (p.out_dtype == ADVGRPO_BF16) {
-                uint2 pk;
-                pk.x = (uint32_t)f2bf(v0) | ((uint32_t)f2bf(v1) << 16);
-                pk.y = (uint32_t)f2bf(v2) | ((uint32_t)f2bf(v3) << 16);
-                *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(p.C) + o) = pk;
+                *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(p.C) + o) = pack4(v0, v1, v2, v3);
             } else {
                 *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.C) + o) = make_float4(v0, v1, v2, v3);
             }

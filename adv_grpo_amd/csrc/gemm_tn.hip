@@ -138,10 +138,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnParams p) {
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
                 const char* a = pb + kc * 32 * 256 + p_off + nb * 32;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
-                const s16x4 hi =
-                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * 256));
-                s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                s16x8 both = ld_tr_s16x8(a, a + 16 * 256);
                 if (ragged) {   // tokens past M were clamped on the way in: zero their contribution (P side suffices)
                     asm volatile("; ragged chunk" ::: "memory");
                     const int mb = m0 + kc * 32 + g * 4;
@@ -156,10 +153,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnParams p) {
 #pragma unroll
             for (int qn = 0; qn < 4; ++qn) {
                 const char* a = qb + kc * 32 * 128 + q_off + qn * 32;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
-                const s16x4 hi =
-                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * 128));
-                qf[qn] = __builtin_bit_cast(bf16x8_t, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                qf[qn] = ld_tr_frag(a, a + 16 * 128);
             }
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
@@ -352,10 +346,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_grouped_kernel(const TnGroup g
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
                 const char* a = pb + kc * 32 * 256 + p_off + nb * 32;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
-                const s16x4 hi =
-                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * 256));
-                s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                s16x8 both = ld_tr_s16x8(a, a + 16 * 256);
                 if (ragged) {
                     asm volatile("; ragged stage" ::: "memory");
                     const int mb = m0 + kc * 32 + g * 4;
@@ -370,10 +361,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_grouped_kernel(const TnGroup g
 #pragma unroll
             for (int qn = 0; qn < 4 * NQB; ++qn) {
                 const char* a = qb + kc * 32 * Q_ROW + q_off + qn * 32;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
-                const s16x4 hi =
-                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * Q_ROW));
-                const bf16x8_t qf = __builtin_bit_cast(bf16x8_t, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                const bf16x8_t qf = ld_tr_frag(a, a + 16 * Q_ROW);
 #pragma unroll
                 for (int nb = 0; nb < 2; ++nb) acc[nb][qn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, pf[nb], acc[nb][qn], 0, 0, 0);
             }

@@ -2,6 +2,7 @@
 
     python scripts/probes/asm_compare.py old.s new.s        two builds of one .hip file
     python scripts/probes/asm_compare.py OLD_DIR NEW_DIR    every X.s of OLD_DIR against NEW_DIR/X.s
+    python scripts/probes/asm_compare.py --allow-reordered OLD NEW      RENAMED and REORDERED (below) count as clean
 
 `make -C adv_grpo_amd/csrc asm [EXPERIMENTS=1]` writes obj/asm/<name>.s (obj-exp/asm/ with EXPERIMENTS=1) for every .hip source with
 that file's own flags; build it in a checkout of the old commit and in the new tree and hand the two directories to this tool.  By hand:
@@ -12,7 +13,15 @@ scratch counts).  Normalised: comments, debug directives, the numbers of local l
 symbol names (a kernel that became a template gets another name and a comdat section).  Kernels are matched by their exact demangled
 name; an old kernel without such a match is also looked up with a trailing `false` template argument of the NEW build stripped (a
 parameter the new build added with a default, such as VARLEN).  The directory mode prints one line per file, and the per-kernel lines
-of the files that are not clean.  Exit status 1 when a kernel (or, in the directory mode, a file) of the old build is missing or differs."""
+of the files that are not clean.
+
+Verdicts per kernel, from the strictest: EQUAL (the normalised lines are the same); RENAMED (the same sequence of instructions once the
+register operands v7, v[2:3], s4, s[0:1], a0, a[0:3] are masked: another register allocation of the same schedule); REORDERED (the same
+multiset of opcodes, operands ignored, in another order -- whether the dependencies are the same is for a run to show; the same
+opcodes in the SAME order with another immediate or offset are not a reordering); DIFFERS.  RENAMED and REORDERED also require an identical .amdhsa_ descriptor (register, scratch and LDS counts): with another
+descriptor the kernel DIFFERS.  Exit status 1 unless every kernel (in the directory mode, every file) of the old build is there and
+EQUAL; with --allow-reordered RENAMED and REORDERED pass as well."""
+import collections
 import difflib
 import os
 import re
@@ -54,8 +63,30 @@ def strip_false(k):
     return re.sub(r"<false>$", "", re.sub(r", false>$", ">", k))
 
 
-def compare(old_text, new_text):
-    """-> (lines of the report, kernels of the old text that are missing or differ, kernels compared)"""
+_REG = re.compile(r"\b[vsa](\d+\b|\[\d+(:\d+)?\])")
+VERDICTS = ("EQUAL", "RENAMED", "REORDERED", "DIFFERS")     # from the strictest
+
+
+def verdict(old_body, new_body):
+    if old_body == new_body:
+        return "EQUAL"
+    def split(body):
+        return [ln for ln in body if ".amdhsa_" not in ln], [ln for ln in body if ".amdhsa_" in ln]
+    (old_ins, old_desc), (new_ins, new_desc) = split(old_body), split(new_body)
+    if old_desc != new_desc:
+        return "DIFFERS"
+    if [_REG.sub("REG", ln) for ln in old_ins] == [_REG.sub("REG", ln) for ln in new_ins]:
+        return "RENAMED"
+    def opcodes(ins):
+        return [ln.split()[0] for ln in ins if ln.strip()]
+    old_ops, new_ops = opcodes(old_ins), opcodes(new_ins)
+    # (the same opcodes in the same order, yet not RENAMED: an immediate, an offset or a wait count changed -- nothing moved)
+    return "REORDERED" if old_ops != new_ops and collections.Counter(old_ops) == collections.Counter(new_ops) else "DIFFERS"
+
+
+def compare(old_text, new_text, allow_reordered=False):
+    """-> (lines of the report, kernels of the old text that are missing or not clean, kernels compared)"""
+    clean = VERDICTS[:3] if allow_reordered else VERDICTS[:1]
     old = {key(k): v for k, v in kernels(old_text).items()}
     new = {key(k): v for k, v in kernels(new_text).items()}
     stripped = {strip_false(k): k for k in new if strip_false(k) != k}
@@ -67,16 +98,16 @@ def compare(old_text, new_text):
             bad += 1
             continue
         used.add(nk)
-        same = body == new[nk]
-        bad += not same
-        lines.append(f"{'EQUAL  ' if same else 'DIFFERS'} {k} ({len(body)} lines)")
-        if not same:
+        v = verdict(body, new[nk])
+        bad += v not in clean
+        lines.append(f"{v:<7} {k} ({len(body)} lines)")
+        if v in VERDICTS[2:]:
             lines += list(difflib.unified_diff(body, new[nk], lineterm="", n=0))[:40]
     lines.append(f"only in the new build: {sorted(k for k in new if k not in used)}")
     return lines, bad, len(old)
 
 
-def compare_dirs(old_dir, new_dir):
+def compare_dirs(old_dir, new_dir, allow_reordered=False):
     lines, bad_files = [], 0
     for name in sorted(f for f in os.listdir(old_dir) if f.endswith(".s")):
         path = os.path.join(new_dir, name)
@@ -84,23 +115,26 @@ def compare_dirs(old_dir, new_dir):
             lines.append(f"MISSING {name}")
             bad_files += 1
             continue
-        sub, bad, n = compare(open(os.path.join(old_dir, name)).read(), open(path).read())
+        sub, bad, n = compare(open(os.path.join(old_dir, name)).read(), open(path).read(), allow_reordered)
         extra = not sub[-1].endswith("[]")
-        lines.append(f"{'DIFFERS' if bad else 'EQUAL  '} {name} ({n} kernels{', ' + str(bad) + ' missing or different' if bad else ''})")
-        if bad or extra:
+        # (a file that is clean only thanks to --allow-reordered is headed by its loosest verdict and lists its kernels)
+        worst = max((VERDICTS.index(ln.split()[0]) for ln in sub if ln.split()[0] in VERDICTS), default=0)
+        lines.append(f"{'DIFFERS' if bad else VERDICTS[worst]:<7} {name} ({n} kernels{', ' + str(bad) + ' missing or different' if bad else ''})")
+        if bad or extra or worst:
             lines += ["    " + ln for ln in sub]
         bad_files += bad > 0
     return lines, bad_files
 
 
-def main(old_path, new_path):
+def main(old_path, new_path, allow_reordered=False):
     if os.path.isdir(old_path):
-        lines, bad = compare_dirs(old_path, new_path)
+        lines, bad = compare_dirs(old_path, new_path, allow_reordered)
     else:
-        lines, bad, _ = compare(open(old_path).read(), open(new_path).read())
+        lines, bad, _ = compare(open(old_path).read(), open(new_path).read(), allow_reordered)
     print("\n".join(lines))
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    paths = [a for a in sys.argv[1:] if a != "--allow-reordered"]
+    sys.exit(main(paths[0], paths[1], allow_reordered=len(paths) != len(sys.argv) - 1))

@@ -130,3 +130,80 @@ def test_directory_mode_reports_per_file(ac, tmp_path, capsys):
     (new / "a.s").unlink()
     assert ac.main(str(old), str(new)) == 1
     assert capsys.readouterr().out.splitlines() == ["MISSING a.s", "EQUAL   b.s (1 kernels)"]
+
+
+# ------------------------------------------------------------------------------------------------ RENAMED and REORDERED
+RENAMED = ["s_load_dwordx2 s[2:3], s[4:5], 0x0", "v_mov_b32_e32 v3, 0", "global_store_dword v3, v0, s[2:3]"]      # other registers
+LONG = ["s_load_dwordx2 s[0:1], s[4:5], 0x0", "v_mov_b32_e32 v1, 0", "v_add_f32_e32 v2, v0, v0", "v_mul_f32_e32 v3, v0, v0",
+        "global_store_dword v1, v2, s[0:1]", "global_store_dword v1, v3, s[0:1] offset:4"]
+MOVED = [LONG[0], LONG[2], LONG[1], LONG[3], LONG[4], LONG[5]]                                                        # two slots swapped
+OTHER_OPCODE = LONG[:3] + ["v_fma_f32 v3, v0, v0, v0"] + LONG[4:]
+
+
+def verdict_of(lines, name):
+    hit = [ln.split()[0] for ln in lines if re.fullmatch(r"\w+\s+" + re.escape(name) + r" \(\d+ lines\)", ln.strip())]
+    assert len(hit) == 1, (name, lines)
+    return hit[0]
+
+
+def test_other_registers_are_renamed(ac):
+    old, new = kernel("_Z11copy_kernelPf", BODY), kernel("_Z11copy_kernelPf", RENAMED)
+    lines, bad, _ = ac.compare(old, new)
+    assert bad == 1 and verdict_of(lines, "copy_kernel") == "RENAMED"
+    lines, bad, _ = ac.compare(old, new, allow_reordered=True)
+    assert bad == 0 and verdict_of(lines, "copy_kernel") == "RENAMED"
+    # an immediate is no register: v1, 0 -> v1, 1 under other register numbers is still a difference
+    lines, bad, _ = ac.compare(old, kernel("_Z11copy_kernelPf", [RENAMED[0], "v_mov_b32_e32 v3, 1", RENAMED[2]]), allow_reordered=True)
+    assert bad == 1 and verdict_of(lines, "copy_kernel") == "DIFFERS"
+
+
+def test_moved_instructions_are_reordered(ac):
+    old, new = kernel("_Z11copy_kernelPf", LONG), kernel("_Z11copy_kernelPf", MOVED)
+    lines, bad, _ = ac.compare(old, new)
+    assert bad == 1 and verdict_of(lines, "copy_kernel") == "REORDERED"
+    assert "+\tv_add_f32_e32 v2, v0, v0" in lines and "-\tv_add_f32_e32 v2, v0, v0" in lines   # the diff is printed: what moved
+    lines, bad, _ = ac.compare(old, new, allow_reordered=True)
+    assert bad == 0 and verdict_of(lines, "copy_kernel") == "REORDERED"
+    lines, bad, _ = ac.compare(old, kernel("_Z11copy_kernelPf", OTHER_OPCODE), allow_reordered=True)     # another multiset of opcodes
+    assert bad == 1 and verdict_of(lines, "copy_kernel") == "DIFFERS"
+
+
+@pytest.mark.parametrize("body,new_body", [(BODY, RENAMED), (LONG, MOVED)])
+def test_another_descriptor_stays_differs(ac, body, new_body):
+    old = kernel("_Z11copy_kernelPf", body)
+    new = kernel("_Z11copy_kernelPf", new_body).replace(".amdhsa_next_free_vgpr 12", ".amdhsa_next_free_vgpr 13")
+    for allow in (False, True):
+        lines, bad, _ = ac.compare(old, new, allow_reordered=allow)
+        assert bad == 1 and verdict_of(lines, "copy_kernel") == "DIFFERS"
+
+
+def test_allow_reordered_exit_status_and_directory_mode(ac, tmp_path, capsys):
+    old, new = tmp_path / "old", tmp_path / "new"
+    old.mkdir()
+    new.mkdir()
+    (old / "a.s").write_text(kernel("_Z11copy_kernelPf", BODY) + kernel("_Z11attn_kernelPf", LONG))
+    (new / "a.s").write_text(kernel("_Z11copy_kernelPf", RENAMED) + kernel("_Z11attn_kernelPf", MOVED))
+    (old / "b.s").write_text(kernel("_Z11norm_kernelILi4ELb0EEvPf", BODY))
+    (new / "b.s").write_text(kernel("_Z11norm_kernelILi4ELb0EEvPf", BODY))
+    assert ac.main(str(old), str(new)) == 1                                   # as before: anything but EQUAL fails
+    out = capsys.readouterr().out.splitlines()
+    assert out[0] == "DIFFERS a.s (2 kernels, 2 missing or different)" and out[-1] == "EQUAL   b.s (1 kernels)"
+    assert ac.main(str(old), str(new), allow_reordered=True) == 0
+    out = capsys.readouterr().out.splitlines()
+    assert out[0] == "REORDERED a.s (2 kernels)" and out[-1] == "EQUAL   b.s (1 kernels)"
+    assert verdict_of(out, "copy_kernel") == "RENAMED" and verdict_of(out, "attn_kernel") == "REORDERED"
+    (new / "b.s").write_text(kernel("_Z11norm_kernelILi4ELb0EEvPf", CHANGED))
+    assert ac.main(str(old), str(new), allow_reordered=True) == 1             # a real difference still fails
+
+
+def test_command_line_flag(tmp_path):
+    import subprocess
+    import sys
+    # (kernel names c++filt leaves alone, so the tool's own demangler call works with or without binutils' table)
+    (tmp_path / "old.s").write_text(kernel("_Z11copy_kernelPf", BODY))
+    (tmp_path / "new.s").write_text(kernel("_Z11copy_kernelPf", RENAMED))
+    run = lambda *flags: subprocess.run([sys.executable, str(_PATH), *flags], capture_output=True, text=True)
+    assert run(str(tmp_path / "old.s"), str(tmp_path / "new.s")).returncode == 1
+    for args in (("--allow-reordered", str(tmp_path / "old.s"), str(tmp_path / "new.s")), (str(tmp_path / "old.s"), str(tmp_path / "new.s"), "--allow-reordered")):
+        r = run(*args)
+        assert r.returncode == 0 and r.stdout.startswith("RENAMED"), r

@@ -120,6 +120,26 @@ def test_attention_output_does_not_depend_on_the_lse_argument(path):
     assert torch.equal(with_lse.contiguous().view(torch.int16), without.contiguous().view(torch.int16)), case["name"]
 
 
+@pytest.mark.parametrize("skv", (257, 65, 320))
+def test_resident_and_tiled_head_dim_80_kernels_agree_bitwise(skv):
+    """attention_fwd_resident_kernel<80> and attention_fwd_kernel<80> share one tile step (csrc/attention.hpp): the same arithmetic in the
+    same order, so the same bits.  257 queries over skv keys take the resident kernel; the same K / V under 513 queries (the first 257 rows
+    the same) take the tiled one.  257 keys: a ragged fifth tile; 65: a ragged tile with one 16-key block; 320: five full tiles."""
+    from adv_grpo_amd import ops
+    B, H, hd, sq = 1, 2, 80, 257
+    g = torch.Generator().manual_seed(8000 + skv)
+    q = torch.randn(B, 513, H * hd, generator=g).to(torch.bfloat16).cuda()
+    k = torch.randn(B, skv, H * hd, generator=g).to(torch.bfloat16).cuda()
+    v = torch.randn(B, skv, H * hd, generator=g).to(torch.bfloat16).cuda()
+    lse_res, lse_til = _sent_f32(B, H, sq), _sent_f32(B, H, 513)
+    o_res = ops.attention(q[:, :sq], k, v, H, lse=lse_res)          # Sq <= 512 and Skv <= 320: resident
+    o_til = ops.attention(q, k, v, H, lse=lse_til)                  # Sq > 512: tiled
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(o_res.float()).all()) and bool(torch.isfinite(lse_res).all())
+    assert torch.equal(o_res.view(torch.int16), o_til[:, :sq].contiguous().view(torch.int16)), "out"
+    assert torch.equal(lse_res.view(torch.int32), lse_til[:, :, :sq].contiguous().view(torch.int32)), "lse"
+
+
 # ---------------------------------------------------------------------------------------------------------------------- backward
 def _run_backward(kw, packed, o, d_o, lse):
     """dq | dk | dv as column slices of ONE sentinel-filled packed buffer [B, S + 1, 3 H hd + 8]; o and d_o with a pitch of their own.
