@@ -453,6 +453,28 @@ def load_qwen_text_encoder(component_dir):
     return read_tensors(component_dir, keys=set(want), rename=_qwen_text_rename), out
 
 
+_QWEN_SCHEDULER_FIELDS = ("num_train_timesteps", "base_image_seq_len", "max_image_seq_len", "base_shift", "max_shift", "shift_terminal")
+
+
+def load_qwen_scheduler(component_dir):
+    """Qwen-Image's scheduler/scheduler_config.json -> the keyword arguments of scheduler.QwenImageFlowMatchScheduler.  A directory
+    without the file gives {} (the published defaults); a file that asks for a schedule this build does not implement is refused."""
+    path = os.path.join(component_dir, "scheduler_config.json")
+    if not os.path.isfile(path):
+        return {}
+    with open(path) as f:
+        cfg = json.load(f)
+    _class(cfg, component_dir, "FlowMatchEulerDiscreteScheduler")
+    _expect(cfg, component_dir, _defaults=dict(use_dynamic_shifting=False, time_shift_type="exponential", use_karras_sigmas=False,
+                                               use_exponential_sigmas=False, use_beta_sigmas=False, invert_sigmas=False, stochastic_sampling=False),
+            use_dynamic_shifting=True, time_shift_type="exponential", use_karras_sigmas=False, use_exponential_sigmas=False,
+            use_beta_sigmas=False, invert_sigmas=False, stochastic_sampling=False)
+    out = {k: cfg[k] for k in _QWEN_SCHEDULER_FIELDS if cfg.get(k) is not None}
+    if "num_train_timesteps" in out:
+        out["num_train_timesteps"] = int(out["num_train_timesteps"])
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------- pipelines
 def pipeline_kind(snapshot_dir):
     """'sd3' | 'qwen' from model_index.json (or from the transformer's class when the index is absent)."""
@@ -488,6 +510,7 @@ def load_pipeline(snapshot_dir, text_encoders=False):
     else:
         out["transformer"] = load_qwen_transformer(sub("transformer"))
         out["vae"] = load_qwen_vae_decoder(sub("vae"))
+        out["scheduler"] = load_qwen_scheduler(sub("scheduler"))
         if text_encoders:
             out["text_encoder"] = load_qwen_text_encoder(sub("text_encoder"))
     return out

@@ -39,7 +39,8 @@ class ReferenceImageStore:
 
     def _load(self, prompt):
         out = []
-        for fname in self.map[prompt]:
+        names = self.map[prompt]
+        for fname in ([names] if isinstance(names, str) else names):     # qwen_generate.py writes one name per prompt, the _multi script a list
             path = os.path.join(self.dir, fname)
             try:
                 out.append(load_image(path, self.res))

@@ -166,6 +166,32 @@ int advgrpo_flow_sde_step_bwd_kl(const void* v_uncond, const void* v_text, int v
                                  void* grad_v_uncond, void* grad_v_text, float* kl_out, void* workspace, int B,
                                  int64_t n, void* stream);
 
+/* ------------------------------------------------------------------ Qwen-Image sampling step
+ * One denoising step of diffusers' QwenImagePipeline.__call__ (the norm-rescaled "true CFG" combine) followed by
+ * FlowMatchEulerDiscreteScheduler.step (the deterministic Euler update), in one pass.  PARITY UNPINNED: restated from the
+ * published pipeline, not checked against an installed diffusers (scripts/verify_against_diffusers.py pins it where one exists).
+ *
+ * v_neg / v_pos (v_dtype) and sample / prev_sample (sample_dtype): [B, C, H, W], bf16 or f32, the UNPACKED tensors
+ * QwenImageTransformer2DModel returns.  A token is one patch_size x patch_size patch across all C channels (the last axis of
+ * diffusers' packed [B, N_img, C * 4] latents).  R = round to bf16 when v_dtype is bf16, the identity when it is f32.  Per token:
+ *
+ *   d    = R(pos - neg) ;  m = R(true_cfg_scale * d) ;  comb = R(neg + m)
+ *   cn   = R(sqrt(sum_f32 pos^2)) ;  nn = R(sqrt(sum_f32 comb^2))            over the token's C * 4 values
+ *   out  = R(comb * R(cn / nn))
+ *   dt   = R(sigma_next - sigma) ;  prev = cast_to_sample_dtype( f32(sample) + f32(R(dt * out)) )
+ *
+ * (torch casts a 0-dim f32 tensor to the other operand's dtype before a multiply: with bf16 predictions dt itself is rounded.)
+ * No epsilon: a token whose comb is all zeros is NaN in that token only, as in the pipeline.  The sums run in a fixed order
+ * (bit-reproducible run to run); they differ from torch.norm's by summation order only.
+ * v_pos == NULL: the single-prediction form (true_cfg_scale <= 1 or no negative prompt), prev = sample + R(R(dt) * v_neg).
+ * sigma / sigma_next: device f32, element b * sigma_stride (stride 0 = one value for all samples), as advgrpo_sde_step: a
+ * captured graph follows the table.  prev_sample may be `sample` itself.  Built for patch_size 2 and C = 16; every tensor
+ * aligned to two of its elements. */
+int advgrpo_qwen_cfg_euler_step(const void* v_neg, const void* v_pos, int v_dtype, float true_cfg_scale,
+                                const void* sample, int sample_dtype,
+                                const float* sigma, const float* sigma_next, int sigma_stride,
+                                void* prev_sample, int B, int C, int H, int W, int patch_size, void* stream);
+
 /* ------------------------------------------------------------------ group advantage
  * PerPromptStatTracker.update(type='grpo') on a fresh tracker -- adv_grpo/stat_tracking.py:18-47:
  * float64, per-group mean over rows, std = global (np.std over all rows, per column) or

@@ -19,6 +19,9 @@ The oracle takes diffusers' own state_dict (weights are keyed by diffusers names
   * QwenImageTransformer2DModel forward (diffusers >= 0.35; reduced depth with --random; non-square latents, two prompts of      -> rel L2 < 1e-4
     different lengths through the pipeline's padding mask) vs oracle/qwen_mmdit.py
   * AutoencoderKLQwenImage.decode on one frame vs oracle/qwen_vae.py                                    -> max abs < 1e-4
+  * Qwen-Image sampling (adv_grpo_amd/qwen_generate.py, scheduler.QwenImageFlowMatchScheduler): the dynamic-shift sigma table      -> |d sigma| < 2e-6
+    against FlowMatchEulerDiscreteScheduler.set_timesteps(sigmas=, mu=), and one true-CFG combine + scheduler.step in bf16 and f32    -> bit-identical
+    against the sequenced restatement (on a GPU also the fused kernel: >= 99 % of the tokens bit-identical)
   * peft: an adapter written by `get_peft_model(...).save_pretrained` read by checkpoint.load_lora, and one written by
     checkpoint.save_lora read by `PeftModel.from_pretrained`                                            -> bit-identical tensors
 Exit status 0 = the restatements are pinned on this machine (non-zero on any mismatch; sections whose package is missing are reported
@@ -207,6 +210,53 @@ def main():
               f"(longest prompt), {r1:.2e} (shorter prompt: padded + masked there, unpadded here)")
         ok &= r0 < 1e-4 and r1 < 1e-4
         del qt, Wq
+
+    # ---------------------------------------------------------------- Qwen-Image sampling: the dynamic-shift schedule and the true-CFG Euler step
+    try:
+        from diffusers.pipelines.qwenimage.pipeline_qwenimage import calculate_shift
+    except ImportError:
+        calculate_shift = None
+        print(f"diffusers {diffusers.__version__} has no QwenImagePipeline: the sampling step and schedule of adv_grpo_amd/qwen_generate.py stay unpinned here")
+    if calculate_shift is not None:
+        import numpy as np
+        from adv_grpo_amd import qwen_generate as o_g
+        from adv_grpo_amd.scheduler import QwenImageFlowMatchScheduler
+        qs = FlowMatchEulerDiscreteScheduler(base_image_seq_len=256, base_shift=0.5, max_image_seq_len=8192, max_shift=0.9, num_train_timesteps=1000,
+                                             shift=1.0, shift_terminal=0.02, time_shift_type="exponential", use_dynamic_shifting=True)
+        ours = QwenImageFlowMatchScheduler()
+        worst = 0.0
+        for n_steps, n_img in ((50, 1024), (28, 4096), (4, 16)):
+            mu = calculate_shift(n_img, 256, 8192, 0.5, 0.9)
+            qs.set_timesteps(sigmas=np.linspace(1.0, 1 / n_steps, n_steps), mu=mu, device="cpu")          # QwenImagePipeline.__call__
+            sig, ts = ours.table(n_steps, n_img)
+            worst = max(worst, float(np.abs(qs.sigmas.numpy() - sig).max()), float(np.abs(qs.timesteps.numpy() - ts).max()) / 1000)
+            ok &= abs(mu - ours.mu(n_img)) < 1e-12
+        print(f"Qwen-Image schedule (dynamic shift, shift_terminal 0.02): max |sigma - diffusers| {worst:.2e} (diffusers evaluates the chain in float32, "
+              "the table here is the float64 chain rounded once)")
+        ok &= worst < 2e-6
+        # the step: QwenImagePipeline.__call__'s combine on packed latents + scheduler.step, against the fused kernel's restatement (and the kernel on a GPU)
+        g = torch.Generator().manual_seed(5)
+        for dt_ in (torch.bfloat16, torch.float32):
+            neg, pos, lat = (torch.randn(2, 16, 16, 24, generator=g).to(device=dev, dtype=dt_) for _ in range(3))
+            qs.set_timesteps(sigmas=np.linspace(1.0, 1 / 50, 50), mu=calculate_shift(96, 256, 8192, 0.5, 0.9), device=dev)
+            ours.set_timesteps(50, 96, device=dev)
+            qs._step_index = None
+            qs._init_step_index(qs.timesteps[10])
+            p_neg, p_pos = o_g._pack(neg), o_g._pack(pos)
+            comb = p_neg + 4.0 * (p_pos - p_neg)                                                           # the pipeline's lines, verbatim in meaning
+            noise_pred = comb * (torch.norm(p_pos, dim=-1, keepdim=True) / torch.norm(comb, dim=-1, keepdim=True))
+            ref = qs.step(noise_pred, qs.timesteps[10], o_g._pack(lat), return_dict=False)[0].to(dt_)
+            ref = o_g._unpack(ref, 16, 16, 24)
+            seq = o_g.cfg_euler_step_sequenced(neg, pos, lat, qs.sigmas.to(dev), 10, 4.0)                  # diffusers' own table: the step alone
+            same = torch.equal(seq, ref)
+            line = f"Qwen-Image true-CFG Euler step ({dt_}): sequenced restatement {'bit-identical' if same else 'DIFFERS'}"
+            ok &= same
+            if str(dev).startswith("cuda"):
+                fused = o_g.cfg_euler_step(neg, pos, lat, qs.sigmas.to(dev).float().contiguous(), 10, 4.0)
+                tok = (o_g._pack(fused) == o_g._pack(ref)).all(dim=-1).double().mean().item()
+                line += f"; fused kernel: {tok:.5f} of the tokens bit-identical"
+                ok &= tok >= 0.99
+            print(line)
 
     # ---------------------------------------------------------------- PEFT's adapter files (TP:389-398 save_ckpt, TP:506-509 load)
     try:
