@@ -140,6 +140,17 @@ SIGNATURES = {
                                              _P, _P, _P, _P, c_int, c_int64, _P]),
     # Qwen-Image's true-CFG combine + Euler step: v_neg, v_pos, v_dtype, scale, sample, dtype, sigma, sigma_next, stride, out, B, C, H, W, patch
     "advgrpo_qwen_cfg_euler_step": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, _P] + [c_int] * 5 + [_P]),
+    # the stochastic steps under the norm-rescaled true CFG: their namesakes' arguments with (B, C, H, W, patch_size) in place of (B, n);
+    # one backward entry each, mean_ref / kl_out / workspace nullable
+    "advgrpo_sde_step_rescaled_workspace_bytes": (c_int64, [c_int] * 5),
+    "advgrpo_sde_step_rescaled": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, c_int, _P, c_uint64,
+                                          c_uint64, _P, c_int, _P, _P, c_int, _P, _P, _P, _P] + [c_int] * 5 + [_P]),
+    "advgrpo_flow_sde_step_rescaled": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P, c_uint64,
+                                               c_uint64, _P, c_int, _P, _P, c_int, _P, _P, _P, _P] + [c_int] * 5 + [_P]),
+    "advgrpo_sde_step_rescaled_bwd": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P, _P, c_float,
+                                              _P, _P, _P, _P] + [c_int] * 5 + [_P]),
+    "advgrpo_flow_sde_step_rescaled_bwd": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, _P, c_int, _P, _P, c_float,
+                                                   _P, _P, _P, _P] + [c_int] * 5 + [_P]),
     "advgrpo_group_advantage": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, _P]),
     "advgrpo_group_advantage_stats": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, _P, _P]),
     "advgrpo_grpo_loss": (c_int, [_P, _P, _P, c_int, c_float, c_float, _P, _P, _P]),

@@ -111,7 +111,7 @@ def output(pipe, latents, output_type, pil):
 def rollout(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, height, width,
             num_inference_steps, mini_num_image_per_prompt, guidance_scale, generator, latents, output_type, joint_attention_kwargs,
             noise_level, train_num_steps, process_index, sample_num_steps, random_timestep, noises, seed, *, branch, keep_f32,
-            sde_type="cps"):
+            sde_type="cps", cfg_rescale=False):
     """The denoise loop of the three text-to-image entry points, for P prompts and G = mini_num_image_per_prompt samples of each.
 
     * ``branch=False`` (pipeline_with_logprob_random): the embeddings repeated G times up front, P * G initial latents, every step on
@@ -123,9 +123,13 @@ def rollout(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, n
     * ``keep_f32`` (pipeline_with_logprob): the latents stay float32 between steps and are rounded to the embedding dtype only at the
       transformer's door; otherwise the fused step's ``cast`` output is the next latent.
     * ``sde_type``: ``"cps"`` (Flow-CPS) or ``"sde"`` (Flow-SDE), handed to ``sde_step_cfg`` for every step.
+    * ``cfg_rescale``: Qwen-Image's norm-rescaled true CFG instead of the SD3 combine in every step (``sde_step_cfg(cfg_rescale=True)``);
+      not with ``branch``: the fan-out step has no rescaled form.  Without CFG (``guidance_scale <= 1``) it changes nothing.
     """
     if prompt_embeds is None:
         raise ValueError(NEED_EMBEDS)
+    if cfg_rescale and branch:
+        raise NotImplementedError("cfg_rescale with a branching rollout: the fan-out step (advgrpo_sde_step_branch) has no rescaled form")
     height = height or self.default_sample_size * self.vae_scale_factor
     width = width or self.default_sample_size * self.vae_scale_factor
     self._guidance_scale = guidance_scale
@@ -180,7 +184,8 @@ def rollout(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, n
         nxt, cast, log_prob, _, _ = sde_step_cfg(                              # PF:640-655, :192-204, :414-429 fused
             self.scheduler, vu, vt, guidance_scale, None, latents, cur,
             noise=None if noises is None else noises[i], seed=seed, offset=(1 + i) * ctr,
-            out_dtype=None if want_f32 else lat_dtype, want_mean=False, step_index=i, sigmas=sigma_table, copies=copies, sde_type=sde_type)
+            out_dtype=None if want_f32 else lat_dtype, want_mean=False, step_index=i, sigmas=sigma_table, copies=copies, sde_type=sde_type,
+            **({"cfg_rescale": True} if cfg_rescale else {}))
         latents = nxt if want_f32 else cast
         if copies is not None:                                                 # PF:163-170, :385-392: the embeddings follow the latents
             P, B = B, B * G

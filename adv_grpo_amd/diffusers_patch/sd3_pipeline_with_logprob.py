@@ -10,6 +10,8 @@ The windowed rollouts (sd3_pipeline_with_logprob_fast.py) record ``train_num_ste
   dtype (PFull:173-184).  The fused step writes both in one pass.  A replayed log-prob is computed from what was stored: on the last
   steps of a schedule, where the Flow-SDE noise scale is ~6e-3, bf16 storage alone would move it by ~2e-2.
 * ``sde_type``: ``"cps"`` -- Flow-CPS, the step the reference's module imports (PFull:8) -- or ``"sde"`` (Flow-SDE, SDE:13-73).
+* ``self.cfg_rescale`` (absent: off): Qwen-Image's norm-rescaled true CFG instead of the SD3 combine in every step (``sde_step_cfg``).  The
+  keyword list above is pinned, so the switch travels on the pipeline object, as ``sde_type`` does for the branching rollouts.
 * Philox counters as in the windowed rollouts: the initial latents from 0, the epsilon of step i in ``[(1 + i) * ctr, (2 + i) * ctr)``.
 """
 import torch
@@ -52,6 +54,7 @@ def pipeline_with_logprob(self, prompt=None, prompt_2=None, prompt_3=None, heigh
     timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device)   # PFull:131-137
     sigma_table = self.scheduler.sigmas                                        # rollout-local view (see _rollout.rollout)
     all_latents, all_log_probs = [latents], []                                 # PFull:142-143
+    cfg_rescale = bool(getattr(self, "cfg_rescale", False))
     ctr = (latents.numel() + 3) // 4 + 1
     mods_all, ctx_rows = hoist(self.transformer, timesteps, tem_pe, tem_ppe)
     for i in range(len(timesteps)):
@@ -60,7 +63,8 @@ def pipeline_with_logprob(self, prompt=None, prompt_2=None, prompt_3=None, heigh
         nxt, cast, log_prob, _, _ = sde_step_cfg(                              # PFull:173-184 fused: the f32 sample and its cast
             self.scheduler, vu, vt, guidance_scale, None, latents, noise_level,
             noise=None if noises is None else noises[i], seed=seed, offset=(1 + i) * ctr,
-            out_dtype=dtype, want_mean=False, step_index=i, sigmas=sigma_table, sde_type=sde_type)
+            out_dtype=dtype, want_mean=False, step_index=i, sigmas=sigma_table, sde_type=sde_type,
+            **({"cfg_rescale": True} if cfg_rescale else {}))
         all_latents.append(nxt)
         all_log_probs.append(log_prob)
         latents = nxt if cast is None else cast

@@ -33,13 +33,14 @@ def pipeline_with_logprob_random(self, prompt=None, prompt_2=None, prompt_3=None
                                  joint_attention_kwargs=None, clip_skip=None,
                                  callback_on_step_end_tensor_inputs=("latents",), max_sequence_length=256,
                                  skip_layer_guidance_scale=2.8, noise_level=0.7, train_num_steps=1, process_index=0,
-                                 sample_num_steps=10, random_timestep=None, noises=None, seed=None, sde_type="cps"):
+                                 sample_num_steps=10, random_timestep=None, noises=None, seed=None, sde_type="cps", cfg_rescale=False):
     """``sde_type``: ``"cps"`` (Flow-CPS, the reference's step for this rollout) or ``"sde"`` (Flow-SDE, SDE:13-73) for the steps of the window;
-    the default reproduces the bits this function always gave."""
+    the default reproduces the bits this function always gave.  ``cfg_rescale=True``: every step combines its two predictions with
+    Qwen-Image's norm-rescaled true CFG (``sde_step_cfg``) instead of the SD3 combine; the latents must be [B, 16, H, W]."""
     return rollout(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, height, width,
                    num_inference_steps, mini_num_image_per_prompt, guidance_scale, generator, latents, output_type, joint_attention_kwargs,
                    noise_level, train_num_steps, process_index, sample_num_steps, random_timestep, noises, seed,
-                   branch=False, keep_f32=False, sde_type=sde_type)
+                   branch=False, keep_f32=False, sde_type=sde_type, cfg_rescale=cfg_rescale)
 
 
 @torch.no_grad()
@@ -71,11 +72,12 @@ def pipeline_with_logprob_new(self, prompt=None, prompt_2=None, prompt_3=None, h
       pipeline_with_logprob_random), anything else the [0, 1] image tensor.
     * the keyword list is the reference's plus ``noises`` / ``seed`` and nothing else, so the choice of step travels on the pipeline object,
       like ``cfg_two_streams``: ``self.sde_type`` = ``"cps"`` (the default when absent) or ``"sde"`` (Flow-SDE, SDE:13-73).
+    * ``self.cfg_rescale`` (Qwen-Image's norm-rescaled true CFG) is read the same way and refused: the fan-out step has no rescaled form.
     The G samples of a group share their initial noise and prefix: the group's spread comes from the SDE window alone."""
     return rollout(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, height, width,
                    num_inference_steps, mini_num_image_per_prompt, guidance_scale, generator, latents, output_type, joint_attention_kwargs,
                    noise_level, train_num_steps, process_index, sample_num_steps, random_timestep, noises, seed,
-                   branch=True, keep_f32=False, sde_type=getattr(self, "sde_type", "cps"))
+                   branch=True, keep_f32=False, sde_type=getattr(self, "sde_type", "cps"), cfg_rescale=getattr(self, "cfg_rescale", False))
 
 
 @torch.no_grad()
@@ -96,4 +98,4 @@ def pipeline_with_logprob(self, prompt=None, prompt_2=None, prompt_3=None, heigh
     return rollout(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, height, width,
                    num_inference_steps, mini_num_image_per_prompt, guidance_scale, generator, latents, output_type, joint_attention_kwargs,
                    noise_level, train_num_steps, process_index, sample_num_steps, random_timestep, noises, seed,
-                   branch=True, keep_f32=True, sde_type=getattr(self, "sde_type", "cps"))
+                   branch=True, keep_f32=True, sde_type=getattr(self, "sde_type", "cps"), cfg_rescale=getattr(self, "cfg_rescale", False))

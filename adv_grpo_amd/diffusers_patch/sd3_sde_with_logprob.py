@@ -8,6 +8,9 @@ folds the CFG combine and the cast back to the latent dtype
 Names: ``sde_step_with_logprob`` and ``sde_step_with_logprob_new`` both mean Flow-CPS here (what the reference's rollouts import under
 either name).  The reference's own ``sde_step_with_logprob`` (SDE:13-73, the original Flow-GRPO step with the full Gaussian log-density) is
 ``flow_sde_step_with_logprob``; ``sde_step_cfg(sde_type="sde")`` is its fused form.
+
+``sde_step_cfg(cfg_rescale=True)`` replaces the SD3 combine by Qwen-Image's norm-rescaled true CFG (qwen_generate.py has the
+deterministic sampler's form of it) in front of either step, still in one launch; ``rescaled_prediction`` is that combine as torch ops.
 """
 import math
 
@@ -31,9 +34,21 @@ def _sigma_tables(scheduler, timestep, B, device):
     return scheduler.sigmas[ii].contiguous(), scheduler.sigmas[ii + 1].contiguous(), 1
 
 
+def rescaled_prediction(v_uncond, v_text, guidance_scale):
+    """Qwen-Image's true-CFG prediction as the torch ops of QwenImagePipeline.__call__, launch by launch, on unpacked [B, C, H, W]
+    predictions: comb = neg + s (pos - neg), then comb * (||pos|| / ||comb||) over each 2 x 2 x C token, in the predictions' dtype."""
+    from ..qwen_generate import _pack, _unpack
+    B, C, H, W = v_uncond.shape
+    neg, pos = _pack(v_uncond), _pack(v_text)
+    comb = neg + guidance_scale * (pos - neg)
+    cond_norm = torch.norm(pos, dim=-1, keepdim=True)
+    noise_norm = torch.norm(comb, dim=-1, keepdim=True)
+    return _unpack(comb * (cond_norm / noise_norm), C, H, W).contiguous()
+
+
 def sde_step_cfg(scheduler, v_uncond, v_text, guidance_scale, timestep, sample, noise_level=0.7,
                  prev_sample=None, noise=None, seed=None, offset=0, out_dtype=None, want_mean=True,
-                 step_index=None, sigmas=None, copies=None, sde_type="cps"):
+                 step_index=None, sigmas=None, copies=None, sde_type="cps", cfg_rescale=False, sequenced=False):
     """Returns (prev_sample_f32_or_None, prev_sample_cast_or_None, log_prob, prev_sample_mean_or_None, std_dev_t).
 
     v_text=None => no CFG.  Exactly one of prev_sample (replay), noise (injected epsilon) or seed
@@ -45,9 +60,26 @@ def sde_step_cfg(scheduler, v_uncond, v_text, guidance_scale, timestep, sample, 
 
     sde_type: "cps" (Flow-CPS, SDE:117-134: log_prob = -mean((x' - mean)^2)) or "sde" (Flow-SDE, SDE:44-71: the Gaussian log-density with
     its 1 / (2 w^2), log w and log sqrt(2 pi) terms; std_dev_t is returned without the sqrt(-dt)).  With "sde" and noise_level == 0 the
-    step is the deterministic x + v * dt and log_prob is NaN, as in the reference."""
+    step is the deterministic x + v * dt and log_prob is NaN, as in the reference.
+
+    cfg_rescale=True (with v_text): Qwen-Image's norm-rescaled true CFG instead of the SD3 combine -- v = comb * ||v_text|| / ||comb|| over
+    each 2 x 2 x 16 token -- fused with the step (advgrpo_sde_step_rescaled / advgrpo_flow_sde_step_rescaled); `sample` must be
+    [B, 16, H, W] with even H, W.  Not with copies=.  With v_text=None it changes nothing.  sequenced=True runs the same rescaled step
+    as separate operations (the torch combine and rescale, then this function's kernel with v_text=None): the check and the
+    benchmark's baseline."""
     if sde_type not in SDE_TYPES:
         raise ValueError(f"sde_step_cfg: sde_type must be one of {SDE_TYPES}, got {sde_type!r}")
+    rescale = bool(cfg_rescale) and v_text is not None
+    if cfg_rescale and copies is not None:
+        raise ValueError("sde_step_cfg(cfg_rescale=True): the fan-out step (copies=) has no rescaled form")
+    if rescale and (sample.dim() != 4 or sample.shape[1] != 16 or v_uncond.shape != sample.shape or v_text.shape != sample.shape
+                    or v_text.dtype != v_uncond.dtype):
+        raise ValueError(f"sde_step_cfg(cfg_rescale=True): predictions and sample must be [B, 16, H, W] tensors of one shape, the "
+                         f"predictions of one dtype; got {tuple(v_uncond.shape)}, {tuple(v_text.shape)}, {tuple(sample.shape)}")
+    if rescale and sequenced:
+        return sde_step_cfg(scheduler, rescaled_prediction(v_uncond, v_text, guidance_scale), None, 1.0, timestep, sample, noise_level,
+                            prev_sample=prev_sample, noise=noise, seed=seed, offset=offset, out_dtype=out_dtype, want_mean=want_mean,
+                            step_index=step_index, sigmas=sigmas, sde_type=sde_type)
     flow = sde_type == "sde"
     lib = _lib.load()
     P = sample.shape[0]
@@ -82,12 +114,18 @@ def sde_step_cfg(scheduler, v_uncond, v_text, guidance_scale, timestep, sample, 
     mean = torch.empty(out_shape, dtype=torch.float32, device=dev) if want_mean else None
     lp = torch.empty(B, dtype=torch.float32, device=dev)
     std = torch.empty(B, dtype=torch.float32, device=dev)
-    ws = torch.empty(max(1, lib.advgrpo_sde_step_workspace_bytes(B, n) // 4), dtype=torch.float32, device=dev)
+    if rescale:
+        shape = (B, *sample.shape[1:], 2)                          # (B, C, H, W, patch_size) in place of (B, n)
+        ws_bytes = lib.advgrpo_sde_step_rescaled_workspace_bytes(*shape)
+    else:
+        shape = ((B,) if copies is None else (P, int(copies))) + (n,)
+        ws_bytes = lib.advgrpo_sde_step_workspace_bytes(B, n)
+    ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device=dev)
     if flow:                                                       # noise_level and a device pointer to sigma_max = sigmas[1] (SDE:46)
-        entry = lib.advgrpo_flow_sde_step if copies is None else lib.advgrpo_flow_sde_step_branch
+        entry = lib.advgrpo_flow_sde_step_rescaled if rescale else lib.advgrpo_flow_sde_step if copies is None else lib.advgrpo_flow_sde_step_branch
         level = (float(noise_level), _lib.ptr(tab[1:2]))
     else:
-        entry = lib.advgrpo_sde_step if copies is None else lib.advgrpo_sde_step_branch
+        entry = lib.advgrpo_sde_step_rescaled if rescale else lib.advgrpo_sde_step if copies is None else lib.advgrpo_sde_step_branch
         level = (float(math.sin(noise_level * math.pi / 2)),)
     _lib.check(entry(
         _lib.ptr(v_uncond), _lib.ptr(v_text), _lib.dtype_code(v_uncond.dtype), float(guidance_scale),
@@ -96,7 +134,7 @@ def sde_step_cfg(scheduler, v_uncond, v_text, guidance_scale, timestep, sample, 
         int(seed or 0), int(offset), _lib.ptr(prev_sample) if replay else None,
         _lib.dtype_code(prev_sample.dtype) if replay else 0, _lib.ptr(nxt), _lib.ptr(cast),
         _lib.dtype_code(cast.dtype) if cast is not None else 0, _lib.ptr(mean), _lib.ptr(lp), _lib.ptr(std),
-        _lib.ptr(ws), *((B,) if copies is None else (P, int(copies))), n, _lib.stream_ptr()))
+        _lib.ptr(ws), *shape, _lib.stream_ptr()))
     return nxt, cast, lp, mean, std.view(-1, *([1] * (sample.dim() - 1)))
 
 

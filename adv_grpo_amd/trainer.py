@@ -166,6 +166,11 @@ class Trainer:
         self.rank, self.world = rank, world
         self.device = pipeline.device
         c = config
+        # opt-in `sample.cfg_rescale`: Qwen-Image's norm-rescaled true CFG in the stochastic steps of rollout, evaluation and replay
+        # (sde_step_cfg(cfg_rescale=True)) instead of the SD3 combine.  Without CFG there is nothing to rescale: a no-op.
+        if c.sample.get("cfg_rescale", False) and c.sample.get("branch_rollout", False):
+            raise NotImplementedError("sample.cfg_rescale with sample.branch_rollout: the fan-out step of the branching rollout has no rescaled form")
+        self.cfg_rescale = bool(c.sample.get("cfg_rescale", False)) and c.sample.guidance_scale > 1
         self.variant = "dino" if any(k.startswith("dino") for k in c.reward_fn.keys()) else "pickscore"
         self.reward_key = next(iter(c.reward_fn.keys()))
         self.reward_fn = rewards.multi_score(self.device, c.reward_fn.to_dict())
@@ -351,6 +356,8 @@ class Trainer:
             self.pipe.sde_type = c.sample.get("sde_type") or "cps"     # always assigned: the pipe never keeps an earlier Trainer's choice
         elif c.sample.get("sde_type") is not None:
             sde_kw = {"sde_type": c.sample.sde_type}
+        if self.cfg_rescale:                                           # (never with the branching rollout: refused at construction)
+            sde_kw["cfg_rescale"] = True
 
         def rollout(i, idx, pe, ppe, ref, prompts):
             # optional pass-through of a prompt mask (Qwen-Image: right-padded prompts of different lengths).  A data source that has
@@ -492,7 +499,8 @@ class Trainer:
                     num_inference_steps=c.sample.eval_num_steps, guidance_scale=c.sample.guidance_scale, output_type="pt",
                     height=c.resolution, width=c.resolution, noise_level=0, mini_num_image_per_prompt=1,
                     process_index=self.rank, sample_num_steps=c.sample.num_steps, random_timestep=c.sample.random_timestep,
-                    generator=gen, **({} if c.sample.get("sde_type") is None else {"sde_type": c.sample.sde_type}))   # TP:303-320
+                    generator=gen, **({} if c.sample.get("sde_type") is None else {"sde_type": c.sample.sde_type}),
+                    **({"cfg_rescale": True} if self.cfg_rescale else {}))                  # TP:303-320
                 if save_folder is not None:
                     names = write_eval_images(images, save_folder, self.rank, batch_idx)    # eval.py:258-266
                     for i, name in zip(idxs, names):
@@ -676,7 +684,8 @@ class Trainer:
                         model, self.pipe.scheduler, s, j, embeds, pooled, s["log_probs"][:, j], s["advantages"][:, j],
                         guidance_scale=c.sample.guidance_scale, noise_level=c.sample.noise_level, adv_clip_max=c.train.adv_clip_max,
                         clip_range=c.train.clip_range, loss_scale=1.0 / (GA * T), step_index=samples["first_step_index"][i] + j,
-                        beta=c.train.beta, sde_type=c.sample.get("sde_type") or "cps", embeds_mask=embeds_mask))
+                        beta=c.train.beta, sde_type=c.sample.get("sde_type") or "cps", embeds_mask=embeds_mask,
+                        **({"cfg_rescale": True} if self.cfg_rescale else {})))
                     for k in ("loss", "approx_kl", "clipfrac", "clipfrac_gt_one", "clipfrac_lt_one", "policy_loss") + \
                             (("kl_loss",) if c.train.beta > 0 else ()):                     # TP:1158-1160
                         agg[k] = agg.get(k, 0) + info[k]

@@ -192,6 +192,67 @@ int advgrpo_qwen_cfg_euler_step(const void* v_neg, const void* v_pos, int v_dtyp
                                 const float* sigma, const float* sigma_next, int sigma_stride,
                                 void* prev_sample, int B, int C, int H, int W, int patch_size, void* stream);
 
+/* ------------------------------------------------------------------ stochastic steps under the norm-rescaled true CFG
+ * Qwen-Image's combine (the section above) in front of the Flow-CPS / Flow-SDE step and its log-prob, in one pass, and the backward
+ * of the replayed step through the norm ratio.  PARITY UNPINNED, as the section above.  The arguments of advgrpo_sde_step /
+ * advgrpo_flow_sde_step with (B, C, H, W, patch_size) in place of (B, n): every tensor is the UNPACKED [B, C, H, W] one, n = C*H*W.
+ * With R as above (bf16 rounding on bf16 predictions), per token:
+ *
+ *   comb = R(neg + R(guidance * R(pos - neg)))          neg = v_uncond, pos = v_text
+ *   v    = R(comb * R(R(sqrt(sum_f32 pos^2)) / R(sqrt(sum_f32 comb^2))))     the sums in advgrpo_qwen_cfg_euler_step's fixed order
+ *
+ * then mean / next / log_prob / std exactly as advgrpo_sde_step (advgrpo_flow_sde_step) computes them from that v: the bits of
+ * that entry fed the rescaled v with v_text == NULL, log_prob up to its summation order.  v_text == NULL: the plain
+ * single-prediction step.  In PHILOX mode element i of sample b draws what advgrpo_sde_step gives it for the same seed / offset
+ * (counter offset + ((b*n + i) >> 2), component (b*n + i) & 3).  log_prob[b] is reduced in f64, in a fixed order, from block
+ * partials that never mix two samples: an all-zero token makes its own sample's log_prob NaN and no other's.
+ * Built for C = 16, patch_size 2, even H and W; every tensor aligned to two of its elements.
+ * workspace: >= advgrpo_sde_step_rescaled_workspace_bytes(B, C, H, W, patch_size) bytes (forward and backward). */
+int64_t advgrpo_sde_step_rescaled_workspace_bytes(int B, int C, int H, int W, int patch_size);
+
+int advgrpo_sde_step_rescaled(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                              const void* x, int x_dtype,
+                              const float* sigma, const float* sigma_prev, int sigma_stride, float sin_coeff,
+                              int mode, const float* eps, uint64_t seed, uint64_t offset,
+                              const void* prev_sample, int prev_dtype,
+                              float* out_next_f32, void* out_next_cast, int out_cast_dtype,
+                              float* out_mean, float* out_log_prob, float* out_std,
+                              void* workspace, int B, int C, int H, int W, int patch_size, void* stream);
+
+int advgrpo_flow_sde_step_rescaled(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                   const void* x, int x_dtype,
+                                   const float* sigma, const float* sigma_prev, int sigma_stride, float noise_level,
+                                   const float* sigma_max,
+                                   int mode, const float* eps, uint64_t seed, uint64_t offset,
+                                   const void* prev_sample, int prev_dtype,
+                                   float* out_next_f32, void* out_next_cast, int out_cast_dtype,
+                                   float* out_mean, float* out_log_prob, float* out_std,
+                                   void* workspace, int B, int C, int H, int W, int patch_size, void* stream);
+
+/* Backward of the replay-mode rescaled step; the arguments of advgrpo_sde_step_bwd_kl (advgrpo_flow_sde_step_bwd_kl) with the
+ * C, H, W shape.  mean_ref == NULL: the policy-only gradient (kl_weight, kl_out and workspace unused).  Per token, with p = pos,
+ * n = neg, c = comb, a = ||p||, b = ||c||, r = a / b as the forward rounded them, s = guidance_scale and
+ *   g = dL/dv = grad_log_prob[b] * (d log_prob / d mean) * (d mean / d v) [+ kl_weight * 2*(mean - mean_ref) * (d mean / d v) / (n*B)]
+ * (mean recomputed from the forward's rounded v):
+ *   dL/dc = r*(g - (c.g)/b^2 * c) ;  grad_v_text = s*dL/dc + (c.g)/(a*b) * p ;  grad_v_uncond = (1 - s)*dL/dc
+ * the gradient of the unrounded formula at the forward's values (autograd's straight-through handling of the bf16 casts).  c.g is
+ * reduced in the order of the norms; all arithmetic f32, one rounding to v_dtype at the store.  kl_out[b] as advgrpo_sde_step_bwd_kl.
+ * Without CFG (v_text NULL) grad_v_uncond = g and grad_v_text is ignored. */
+int advgrpo_sde_step_rescaled_bwd(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                  const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                  int sigma_stride, float sin_coeff, const void* prev_sample, int prev_dtype,
+                                  const float* grad_log_prob, const float* mean_ref, float kl_weight,
+                                  void* grad_v_uncond, void* grad_v_text, float* kl_out, void* workspace,
+                                  int B, int C, int H, int W, int patch_size, void* stream);
+
+int advgrpo_flow_sde_step_rescaled_bwd(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                       const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                       int sigma_stride, float noise_level, const float* sigma_max,
+                                       const void* prev_sample, int prev_dtype,
+                                       const float* grad_log_prob, const float* mean_ref, float kl_weight,
+                                       void* grad_v_uncond, void* grad_v_text, float* kl_out, void* workspace,
+                                       int B, int C, int H, int W, int patch_size, void* stream);
+
 /* ------------------------------------------------------------------ group advantage
  * PerPromptStatTracker.update(type='grpo') on a fresh tracker -- adv_grpo/stat_tracking.py:18-47:
  * float64, per-group mean over rows, std = global (np.std over all rows, per column) or

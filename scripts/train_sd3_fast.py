@@ -64,6 +64,10 @@ def build_parser():
     ap.add_argument("--sde-type", default=None, choices=["cps", "sde"],
                     help="sample.sde_type: the stochastic step of rollout and replay -- cps (Flow-CPS, the default when the config has no "
                          "such key) or sde (the original Flow-GRPO SDE with the full Gaussian log-density)")
+    ap.add_argument("--cfg-rescale", action="store_true",
+                    help="sample.cfg_rescale: combine the two predictions of every rollout, evaluation and replay step with Qwen-Image's "
+                         "norm-rescaled true CFG (comb * ||cond|| / ||comb|| per 2 x 2 token) instead of the SD3 combine; 16-channel latents, "
+                         "not with --branch-rollout")
     ap.add_argument("--lora-mode", default="merged", choices=["merged", "side"],
                     help="merged: LoRA folded into the bf16 weights (default); side: PEFT's side-path arithmetic (TP:490-511)")
     ap.add_argument("--no-train-d", action="store_true", help="keep the discriminator frozen: every epoch is a G-step epoch")
@@ -88,6 +92,21 @@ def build_parser():
     ap.add_argument("--aesthetic-head", default=None, metavar="FILE",
                     help="the aesthetic predictor's sac+logos+ava1-l14-linearMSE.pth (needed by the aesthetic reward)")
     return ap
+
+
+def apply_sample_flags(cfg, args):
+    """The rollout switches of the command line -> config.sample (a key is written only when its flag is given)."""
+    if args.groups_in_flight:
+        cfg.sample.groups_in_flight = args.groups_in_flight
+    if args.cfg_streams:
+        cfg.sample.cfg_two_streams = True
+    if args.branch_rollout:
+        cfg.sample.branch_rollout = True
+    if args.sde_type:
+        cfg.sample.sde_type = args.sde_type
+    if args.cfg_rescale:
+        cfg.sample.cfg_rescale = True
+    return cfg
 
 
 def main():
@@ -128,14 +147,7 @@ def main():
     if args.images_per_prompt:
         cfg.sample.num_image_per_prompt = args.images_per_prompt
         cfg.sample.mini_num_image_per_prompt = min(cfg.sample.mini_num_image_per_prompt, args.images_per_prompt)     # G = 4 (config 4)
-    if args.groups_in_flight:
-        cfg.sample.groups_in_flight = args.groups_in_flight
-    if args.cfg_streams:
-        cfg.sample.cfg_two_streams = True
-    if args.branch_rollout:
-        cfg.sample.branch_rollout = True
-    if args.sde_type:
-        cfg.sample.sde_type = args.sde_type
+    apply_sample_flags(cfg, args)
     if args.no_train_d:
         cfg.train_d = False
     if args.batches:
