@@ -115,42 +115,34 @@ class Fp8Scales(ctypes.Structure):
 _CLIP_TOWER = [_P, _P, _P, c_int, POINTER(VitLayer), c_int, _P, _P, _P]
 _T5_TOWER = [_P, _P, c_int, _P, c_int, c_int, POINTER(c_void_p), c_int, _P]
 
+# the twelve step entries advgrpo_{,flow_}sde_step{,_branch,_bwd,_bwd_kl,_rescaled,_rescaled_bwd}: head + tail + shape + stream
+#   head:   v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride, sin_coeff | noise_level; the
+#           Flow-SDE siblings take `const float* sigma_max` after the noise level
+#   fwd:    mode, eps, seed, offset, prev_sample, prev_dtype, out_next_f32, out_next_cast, out_cast_dtype, out_mean, out_log_prob,
+#           out_std, workspace
+#   bwd:    prev_sample, prev_dtype, grad_log_prob, [mean_ref, kl_weight,] grad_v_uncond, grad_v_text [, kl_out, workspace]
+#           (the rescaled entries have the one backward with the KL arguments, mean_ref / kl_out / workspace nullable)
+#   shape:  (B, n) | the fan-out step's (P, G, n) | the norm-rescaled true CFG's (B, C, H, W, patch_size)
+_STEP_HEAD = [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float]
+_STEP_FWD = [c_int, _P, c_uint64, c_uint64, _P, c_int, _P, _P, c_int, _P, _P, _P, _P]
+_STEP_BWD = [_P, c_int, _P, _P, _P]
+_STEP_BWD_KL = [_P, c_int, _P, _P, c_float, _P, _P, _P, _P]
+_STEP_FLAT, _STEP_FAN, _STEP_TOKENS = [c_int, c_int64], [c_int, c_int, c_int64], [c_int] * 5
+
 # name -> (restype, argtypes); must list every function include/advgrpo.h declares
 SIGNATURES = {
     "advgrpo_abi_version": (c_int, []),
     "advgrpo_last_error": (ctypes.c_char_p, []),
     "advgrpo_randn": (c_int, [_P, c_int, c_int64, c_uint64, c_uint64, _P]),
     "advgrpo_sde_step_workspace_bytes": (c_int64, [c_int, c_int64]),
-    "advgrpo_sde_step": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, c_int, _P, c_uint64,
-                                 c_uint64, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int64, _P]),
-    "advgrpo_sde_step_branch": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, c_int, _P, c_uint64,
-                                        c_uint64, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int64, _P]),
-    "advgrpo_sde_step_bwd": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P, _P,
-                                     _P, c_int, c_int64, _P]),
-    "advgrpo_sde_step_bwd_kl": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P, _P, c_float,
-                                        _P, _P, _P, _P, c_int, c_int64, _P]),
-    # the Flow-SDE siblings: the arguments of their Flow-CPS namesakes with `const float* sigma_max` after the noise level
-    "advgrpo_flow_sde_step": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P, c_uint64,
-                                      c_uint64, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int64, _P]),
-    "advgrpo_flow_sde_step_branch": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P, c_uint64,
-                                             c_uint64, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, c_int64, _P]),
-    "advgrpo_flow_sde_step_bwd": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, _P, c_int, _P, _P,
-                                          _P, c_int, c_int64, _P]),
-    "advgrpo_flow_sde_step_bwd_kl": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, _P, c_int, _P, _P, c_float,
-                                             _P, _P, _P, _P, c_int, c_int64, _P]),
+    **{f"advgrpo_{flow}sde_step{suffix}": (c_int, head + tail + shape + [_P])
+       for flow, head in (("", _STEP_HEAD), ("flow_", _STEP_HEAD + [_P]))
+       for suffix, tail, shape in (("", _STEP_FWD, _STEP_FLAT), ("_branch", _STEP_FWD, _STEP_FAN), ("_bwd", _STEP_BWD, _STEP_FLAT),
+                                   ("_bwd_kl", _STEP_BWD_KL, _STEP_FLAT), ("_rescaled", _STEP_FWD, _STEP_TOKENS),
+                                   ("_rescaled_bwd", _STEP_BWD_KL, _STEP_TOKENS))},
     # Qwen-Image's true-CFG combine + Euler step: v_neg, v_pos, v_dtype, scale, sample, dtype, sigma, sigma_next, stride, out, B, C, H, W, patch
     "advgrpo_qwen_cfg_euler_step": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, _P] + [c_int] * 5 + [_P]),
-    # the stochastic steps under the norm-rescaled true CFG: their namesakes' arguments with (B, C, H, W, patch_size) in place of (B, n);
-    # one backward entry each, mean_ref / kl_out / workspace nullable
     "advgrpo_sde_step_rescaled_workspace_bytes": (c_int64, [c_int] * 5),
-    "advgrpo_sde_step_rescaled": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, c_int, _P, c_uint64,
-                                          c_uint64, _P, c_int, _P, _P, c_int, _P, _P, _P, _P] + [c_int] * 5 + [_P]),
-    "advgrpo_flow_sde_step_rescaled": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P, c_uint64,
-                                               c_uint64, _P, c_int, _P, _P, c_int, _P, _P, _P, _P] + [c_int] * 5 + [_P]),
-    "advgrpo_sde_step_rescaled_bwd": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P, _P, c_float,
-                                              _P, _P, _P, _P] + [c_int] * 5 + [_P]),
-    "advgrpo_flow_sde_step_rescaled_bwd": (c_int, [_P, _P, c_int, c_float, _P, c_int, _P, _P, c_int, c_float, _P, _P, c_int, _P, _P, c_float,
-                                                   _P, _P, _P, _P] + [c_int] * 5 + [_P]),
     "advgrpo_group_advantage": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, _P]),
     "advgrpo_group_advantage_stats": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, _P, _P]),
     "advgrpo_grpo_loss": (c_int, [_P, _P, _P, c_int, c_float, c_float, _P, _P, _P]),

@@ -17,8 +17,6 @@
 //
 // Built with -ffp-contract=off: every reference torch op is one f32 rounding here too, so
 // mean / next are bit-exact with the torch-CPU oracle; log_prob differs by summation order only.
-#include <type_traits>
-
 #include "common.hpp"
 #include "qwen_token.hpp"
 
@@ -591,204 +589,73 @@ extern "C" int64_t advgrpo_sde_step_workspace_bytes(int B, int64_t n) {
     return (int64_t)B * sde_blocks(n) * sizeof(float);
 }
 
-static int check_common(int v_dtype, int x_dtype, int B, int64_t n) {
-    ADVGRPO_CHECK(v_dtype == ADVGRPO_F32 || v_dtype == ADVGRPO_BF16, "sde_step: bad v_dtype %d", v_dtype);
-    ADVGRPO_CHECK(x_dtype == ADVGRPO_F32 || x_dtype == ADVGRPO_BF16, "sde_step: bad x_dtype %d", x_dtype);
-    ADVGRPO_CHECK(B > 0 && n > 0 && n % SDE_VEC == 0, "sde_step: need B>0 and n %% 8 == 0 (B=%d n=%lld)", B,
-                  (long long)n);
-    return 0;
-}
-
-// The four entry shapes, once for both steps.  Step = CpsStep: level = sin_coeff, sigma_max unused (NULL); Step = FlowStep: level =
-// noise_level, sigma_max required.  `what` names the entry in error messages.
-template <class Step>
-static int step_finalize(const float* ws, int nb, int64_t n, float* out_log_prob, int B, const float* sigma, const float* sigma_prev,
-                         int sigma_stride, int P, float level, const float* sigma_max, void* stream) {
-    if constexpr (std::is_same_v<Step, FlowStep>) {
-        hipLaunchKernelGGL(flow_sde_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream), ws, nb, n, out_log_prob, B,
-                           sigma, sigma_prev, sigma_stride, P, level, sigma_max);
-    } else {
-        hipLaunchKernelGGL(sde_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream), ws, nb, n, out_log_prob, B, -1.0f);
+// ---- the twelve step entries: one call block, one forward and one backward routine under them ------------------------------------
+// What any of advgrpo_{,flow_}sde_step{,_branch,_bwd,_bwd_kl} and advgrpo_{,flow_}sde_step_rescaled{,_bwd} receives.  An entry fills
+// it BY NAME (STEP_CALL and the macros after it: the entries spell their parameters alike, so no list is handed on by position) and
+// calls step_forward or step_backward.  Where the entries' checks differ, a field below says so; none of the differences is resolved.
+enum StepShape { STEP_FLAT, STEP_FAN, STEP_TOKENS };
+struct StepCall {
+    const char* what;           // the entry's name in error texts
+    const char* common_what;    // ... in the dtype and B / n checks: "sde_step" under all eight flat and fan-out entries
+    bool flow;                  // Flow-SDE: level = noise_level, sigma_max required; else Flow-CPS: level = sin_coeff, sigma_max NULL
+    const float* sigma_max;
+    // shared inputs
+    const void *v_uncond, *v_text, *x;
+    int v_dtype, x_dtype, sigma_stride;
+    float guidance_scale, level;
+    const float *sigma, *sigma_prev;
+    // forward
+    int mode, prev_dtype, out_cast_dtype;   // (prev_sample / prev_dtype: the backward's too)
+    const float* eps;
+    uint64_t seed, offset;
+    const void* prev_sample;
+    void* out_next_cast;
+    float *out_next_f32, *out_mean, *out_log_prob, *out_std;
+    // backward; mean_ref == NULL: the policy-only backward (kl_weight, kl_out and workspace unused)
+    const float *grad_log_prob, *mean_ref;
+    float kl_weight;
+    void *grad_v_uncond, *grad_v_text;
+    float* kl_out;
+    bool need_mean_ref;         // *_bwd_kl refuse a NULL mean_ref; under *_rescaled_bwd it selects the policy-only backward
+    void *workspace, *stream;
+    // the shape, in one of three forms
+    StepShape shape;
+    bool io_dtypes;             // refuse a bad prev_dtype / out_cast_dtype: the rescaled entries only
+    int B, G;                   // input rows (the fan-out entries' P) and copies per row (1 except there): B * G output rows
+    int64_t n;                  // elements per row (STEP_TOKENS: from rs_layout)
+    int C, H, W, patch_size;
+    StepCall& flat(int B_, int64_t n_) { return shape = STEP_FLAT, common_what = "sde_step", io_dtypes = false, B = B_, G = 1, n = n_, *this; }
+    StepCall& fan(int P_, int G_, int64_t n_) { return shape = STEP_FAN, common_what = "sde_step", io_dtypes = false, B = P_, G = G_, n = n_, *this; }
+    StepCall& tokens(int B_, int C_, int H_, int W_, int patch_) {
+        return shape = STEP_TOKENS, common_what = what, io_dtypes = true, B = B_, G = 1, n = 0, C = C_, H = H_, W = W_, patch_size = patch_, *this;
     }
-    ADVGRPO_LAUNCH_CHECK();
-    return 0;
-}
+};
+#define STEP_CALL(c, NAME, FLOW, LEVEL, SIGMA_MAX)                                                                                  \
+    StepCall c{};                                                                                                                   \
+    c.what = NAME, c.flow = FLOW, c.level = LEVEL, c.sigma_max = SIGMA_MAX, c.v_uncond = v_uncond, c.v_text = v_text,               \
+    c.v_dtype = v_dtype, c.guidance_scale = guidance_scale, c.x = x, c.x_dtype = x_dtype, c.sigma = sigma, c.sigma_prev = sigma_prev, \
+    c.sigma_stride = sigma_stride, c.stream = stream
+#define STEP_FORWARD(c)                                                                                                             \
+    c.mode = mode, c.eps = eps, c.seed = seed, c.offset = offset, c.prev_sample = prev_sample, c.prev_dtype = prev_dtype,           \
+    c.out_next_f32 = out_next_f32, c.out_next_cast = out_next_cast, c.out_cast_dtype = out_cast_dtype, c.out_mean = out_mean,       \
+    c.out_log_prob = out_log_prob, c.out_std = out_std, c.workspace = workspace
+#define STEP_BACKWARD(c)                                                                                                            \
+    c.prev_sample = prev_sample, c.prev_dtype = prev_dtype, c.grad_log_prob = grad_log_prob, c.grad_v_uncond = grad_v_uncond,       \
+    c.grad_v_text = grad_v_text
+#define STEP_KL(c, NEED_MEAN_REF)                                                                                                   \
+    c.mean_ref = mean_ref, c.kl_weight = kl_weight, c.kl_out = kl_out, c.workspace = workspace, c.need_mean_ref = NEED_MEAN_REF
 
-template <class Step>
-static int step_fwd(const char* what, const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale, const void* x,
-                    int x_dtype, const float* sigma, const float* sigma_prev, int sigma_stride, float level,
-                    const float* sigma_max, int mode, const float* eps, uint64_t seed, uint64_t offset, const void* prev_sample,
-                    int prev_dtype, float* out_next_f32, void* out_next_cast, int out_cast_dtype, float* out_mean,
-                    float* out_log_prob, float* out_std, void* workspace, int B, int64_t n, void* stream) {
-    if (check_common(v_dtype, x_dtype, B, n)) return -1;
-    ADVGRPO_CHECK(v_uncond && x && sigma && sigma_prev && out_log_prob && workspace, "%s: null argument", what);
-    ADVGRPO_CHECK((!std::is_same_v<Step, FlowStep>) || sigma_max, "%s: null sigma_max", what);
-    ADVGRPO_CHECK(mode >= 0 && mode <= 2, "%s: bad mode %d", what, mode);
-    ADVGRPO_CHECK(mode != ADVGRPO_SDE_EPS || eps, "%s: mode EPS needs eps", what);
-    ADVGRPO_CHECK(mode != ADVGRPO_SDE_REPLAY || prev_sample, "%s: mode REPLAY needs prev_sample", what);
-    const int nb = sde_blocks(n);
-    hipLaunchKernelGGL(sde_step_kernel<Step>, dim3(nb, B), dim3(SDE_THREADS), 0, as_stream(stream), v_uncond, v_text,
-                       v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride, level, sigma_max, mode, eps,
-                       seed, offset, prev_sample, prev_dtype, out_next_f32, out_next_cast, out_cast_dtype, out_mean,
-                       (float*)workspace, out_std, n);
-    ADVGRPO_LAUNCH_CHECK();
-    return step_finalize<Step>((const float*)workspace, nb, n, out_log_prob, B, sigma, sigma_prev, sigma_stride, B, level, sigma_max,
-                               stream);
-}
-
-template <class Step>
-static int step_branch(const char* what, const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale, const void* x,
-                       int x_dtype, const float* sigma, const float* sigma_prev, int sigma_stride, float level,
-                       const float* sigma_max, int mode, const float* eps, uint64_t seed, uint64_t offset,
-                       const void* prev_sample, int prev_dtype, float* out_next_f32, void* out_next_cast, int out_cast_dtype,
-                       float* out_mean, float* out_log_prob, float* out_std, void* workspace, int P, int G, int64_t n,
-                       void* stream) {
-    ADVGRPO_CHECK(P > 0 && G > 0, "%s: need P>0 and G>0 (P=%d G=%d)", what, P, G);
-    if (check_common(v_dtype, x_dtype, P, n)) return -1;
-    const int gz = (G + SDE_BRANCH_COPIES - 1) / SDE_BRANCH_COPIES;
-    ADVGRPO_CHECK(P <= 65535 && gz <= 65535 && (int64_t)P * G <= INT32_MAX, "%s: P=%d G=%d too large", what, P, G);
-    ADVGRPO_CHECK(v_uncond && x && sigma && sigma_prev && out_log_prob && workspace, "%s: null argument", what);
-    ADVGRPO_CHECK((!std::is_same_v<Step, FlowStep>) || sigma_max, "%s: null sigma_max", what);
-    ADVGRPO_CHECK(mode >= 0 && mode <= 2, "%s: bad mode %d", what, mode);
-    ADVGRPO_CHECK(mode != ADVGRPO_SDE_EPS || eps, "%s: mode EPS needs eps", what);
-    ADVGRPO_CHECK(mode != ADVGRPO_SDE_REPLAY || prev_sample, "%s: mode REPLAY needs prev_sample", what);
-    const int nb = sde_blocks(n), B = P * G;
-    hipLaunchKernelGGL(sde_step_branch_kernel<Step>, dim3(nb, P, gz), dim3(SDE_THREADS), 0, as_stream(stream), v_uncond, v_text,
-                       v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride, level, sigma_max, mode, eps,
-                       seed, offset, prev_sample, prev_dtype, out_next_f32, out_next_cast, out_cast_dtype, out_mean,
-                       (float*)workspace, out_std, P, G, n);
-    ADVGRPO_LAUNCH_CHECK();
-    return step_finalize<Step>((const float*)workspace, nb, n, out_log_prob, B, sigma, sigma_prev, sigma_stride, P, level, sigma_max,
-                               stream);
-}
-
-// mean_ref == NULL: the policy-only backward (kl_weight, kl_out and workspace unused)
-template <class Step>
-static int step_bwd(const char* what, const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale, const void* x,
-                    int x_dtype, const float* sigma, const float* sigma_prev, int sigma_stride, float level,
-                    const float* sigma_max, const void* prev_sample, int prev_dtype, const float* grad_log_prob, bool with_kl,
-                    const float* mean_ref, float kl_weight, void* grad_v_uncond, void* grad_v_text, float* kl_out, void* workspace,
-                    int B, int64_t n, void* stream) {
-    if (check_common(v_dtype, x_dtype, B, n)) return -1;
-    ADVGRPO_CHECK(v_uncond && x && sigma && sigma_prev && prev_sample && grad_log_prob && grad_v_uncond &&
-                      (!with_kl || (mean_ref && kl_out && workspace)), "%s: null argument", what);
-    ADVGRPO_CHECK((!std::is_same_v<Step, FlowStep>) || sigma_max, "%s: null sigma_max", what);
-    ADVGRPO_CHECK(!v_text || grad_v_text, "%s: CFG needs grad_v_text", what);
-    const int nb = sde_blocks(n);
-    hipLaunchKernelGGL(sde_step_bwd_kernel<Step>, dim3(nb, B), dim3(SDE_THREADS), 0, as_stream(stream), v_uncond, v_text,
-                       v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride, level, sigma_max, prev_sample,
-                       prev_dtype, grad_log_prob, grad_v_uncond, grad_v_text, n, with_kl ? mean_ref : (const float*)nullptr,
-                       with_kl ? kl_weight : 0.f, B, with_kl ? (float*)workspace : (float*)nullptr);
-    ADVGRPO_LAUNCH_CHECK();
-    if (with_kl) {
-        hipLaunchKernelGGL(sde_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream),
-                           (const float*)workspace, nb, n, kl_out, B, 1.0f);
-        ADVGRPO_LAUNCH_CHECK();
-    }
-    return 0;
-}
-
-extern "C" int advgrpo_sde_step(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
-                                const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
-                                int sigma_stride, float sin_coeff, int mode, const float* eps, uint64_t seed,
-                                uint64_t offset, const void* prev_sample, int prev_dtype, float* out_next_f32,
-                                void* out_next_cast, int out_cast_dtype, float* out_mean, float* out_log_prob,
-                                float* out_std, void* workspace, int B, int64_t n, void* stream) {
-    return step_fwd<CpsStep>("sde_step", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride,
-                             sin_coeff, nullptr, mode, eps, seed, offset, prev_sample, prev_dtype, out_next_f32, out_next_cast,
-                             out_cast_dtype, out_mean, out_log_prob, out_std, workspace, B, n, stream);
-}
-
-extern "C" int advgrpo_sde_step_branch(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
-                                       const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
-                                       int sigma_stride, float sin_coeff, int mode, const float* eps, uint64_t seed,
-                                       uint64_t offset, const void* prev_sample, int prev_dtype, float* out_next_f32,
-                                       void* out_next_cast, int out_cast_dtype, float* out_mean, float* out_log_prob,
-                                       float* out_std, void* workspace, int P, int G, int64_t n, void* stream) {
-    return step_branch<CpsStep>("sde_step_branch", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev,
-                                sigma_stride, sin_coeff, nullptr, mode, eps, seed, offset, prev_sample, prev_dtype, out_next_f32,
-                                out_next_cast, out_cast_dtype, out_mean, out_log_prob, out_std, workspace, P, G, n, stream);
-}
-
-extern "C" int advgrpo_sde_step_bwd(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
-                                    const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
-                                    int sigma_stride, float sin_coeff, const void* prev_sample, int prev_dtype,
-                                    const float* grad_log_prob, void* grad_v_uncond, void* grad_v_text, int B,
-                                    int64_t n, void* stream) {
-    return step_bwd<CpsStep>("sde_step_bwd", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride,
-                             sin_coeff, nullptr, prev_sample, prev_dtype, grad_log_prob, false, nullptr, 0.f, grad_v_uncond,
-                             grad_v_text, nullptr, nullptr, B, n, stream);
-}
-
-extern "C" int advgrpo_sde_step_bwd_kl(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
-                                       const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
-                                       int sigma_stride, float sin_coeff, const void* prev_sample, int prev_dtype,
-                                       const float* grad_log_prob, const float* mean_ref, float kl_weight,
-                                       void* grad_v_uncond, void* grad_v_text, float* kl_out, void* workspace, int B,
-                                       int64_t n, void* stream) {
-    return step_bwd<CpsStep>("sde_step_bwd_kl", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev,
-                             sigma_stride, sin_coeff, nullptr, prev_sample, prev_dtype, grad_log_prob, true, mean_ref, kl_weight,
-                             grad_v_uncond, grad_v_text, kl_out, workspace, B, n, stream);
-}
-
-extern "C" int advgrpo_flow_sde_step(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
-                                     const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
-                                     int sigma_stride, float noise_level, const float* sigma_max, int mode, const float* eps,
-                                     uint64_t seed, uint64_t offset, const void* prev_sample, int prev_dtype,
-                                     float* out_next_f32, void* out_next_cast, int out_cast_dtype, float* out_mean,
-                                     float* out_log_prob, float* out_std, void* workspace, int B, int64_t n, void* stream) {
-    return step_fwd<FlowStep>("flow_sde_step", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev, sigma_stride,
-                              noise_level, sigma_max, mode, eps, seed, offset, prev_sample, prev_dtype, out_next_f32, out_next_cast,
-                              out_cast_dtype, out_mean, out_log_prob, out_std, workspace, B, n, stream);
-}
-
-extern "C" int advgrpo_flow_sde_step_branch(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
-                                            const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
-                                            int sigma_stride, float noise_level, const float* sigma_max, int mode,
-                                            const float* eps, uint64_t seed, uint64_t offset, const void* prev_sample,
-                                            int prev_dtype, float* out_next_f32, void* out_next_cast, int out_cast_dtype,
-                                            float* out_mean, float* out_log_prob, float* out_std, void* workspace, int P, int G,
-                                            int64_t n, void* stream) {
-    return step_branch<FlowStep>("flow_sde_step_branch", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev,
-                                 sigma_stride, noise_level, sigma_max, mode, eps, seed, offset, prev_sample, prev_dtype,
-                                 out_next_f32, out_next_cast, out_cast_dtype, out_mean, out_log_prob, out_std, workspace, P, G, n,
-                                 stream);
-}
-
-extern "C" int advgrpo_flow_sde_step_bwd(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
-                                         const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
-                                         int sigma_stride, float noise_level, const float* sigma_max, const void* prev_sample,
-                                         int prev_dtype, const float* grad_log_prob, void* grad_v_uncond, void* grad_v_text,
-                                         int B, int64_t n, void* stream) {
-    return step_bwd<FlowStep>("flow_sde_step_bwd", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev,
-                              sigma_stride, noise_level, sigma_max, prev_sample, prev_dtype, grad_log_prob, false, nullptr, 0.f,
-                              grad_v_uncond, grad_v_text, nullptr, nullptr, B, n, stream);
-}
-
-extern "C" int advgrpo_flow_sde_step_bwd_kl(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
-                                            const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
-                                            int sigma_stride, float noise_level, const float* sigma_max,
-                                            const void* prev_sample, int prev_dtype, const float* grad_log_prob,
-                                            const float* mean_ref, float kl_weight, void* grad_v_uncond, void* grad_v_text,
-                                            float* kl_out, void* workspace, int B, int64_t n, void* stream) {
-    return step_bwd<FlowStep>("flow_sde_step_bwd_kl", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev,
-                              sigma_stride, noise_level, sigma_max, prev_sample, prev_dtype, grad_log_prob, true, mean_ref,
-                              kl_weight, grad_v_uncond, grad_v_text, kl_out, workspace, B, n, stream);
-}
-
-// ---- the norm-rescaled true-CFG forms: shape checks, layout choice and grid, once for the four entries
-struct RsLaunch {
-    bool pair;      // two tokens per lane
+struct StepGrid {
+    bool pair;      // STEP_TOKENS: two tokens per lane
     int nb;         // blocks per sample
     int64_t n;      // elements per sample
 };
+static int fan_blocks(int G) { return (G + SDE_BRANCH_COPIES - 1) / SDE_BRANCH_COPIES; }
 static int64_t rs_blocks(int H, int W, int tpl) {
     const int64_t units = (int64_t)(H / 2) * ((W / 2) / tpl);
     return (units + QS_LANES - 1) / QS_LANES;
 }
-static int rs_shape(const char* what, int v_dtype, int x_dtype, int B, int C, int H, int W, int patch_size, int sigma_stride) {
-    ADVGRPO_CHECK(v_dtype == ADVGRPO_F32 || v_dtype == ADVGRPO_BF16, "%s: bad v_dtype %d", what, v_dtype);
-    ADVGRPO_CHECK(x_dtype == ADVGRPO_F32 || x_dtype == ADVGRPO_BF16, "%s: bad x_dtype %d", what, x_dtype);
+static int rs_shape(const char* what, int B, int C, int H, int W, int patch_size, int sigma_stride) {
     ADVGRPO_CHECK(patch_size == 2 && C == QS_CPW * QS_WAVES, "%s: built for patch 2 and C = %d (patch=%d C=%d)", what,
                   QS_CPW * QS_WAVES, patch_size, C);
     ADVGRPO_CHECK(B > 0 && B <= 65535 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && sigma_stride >= 0,
@@ -797,7 +664,7 @@ static int rs_shape(const char* what, int v_dtype, int x_dtype, int B, int C, in
     return 0;
 }
 // ptrs / sizes: every tensor the kernel reads or writes N elements at a time, with its element size (NULL entries are skipped)
-static int rs_layout(const char* what, const void* const* ptrs, const int* sizes, int count, int C, int H, int W, RsLaunch* L) {
+static int rs_layout(const char* what, const void* const* ptrs, const int* sizes, int count, int C, int H, int W, StepGrid* L) {
     auto aligned = [&](int elems) {
         for (int i = 0; i < count; ++i)
             if (ptrs[i] && (uintptr_t)ptrs[i] % (uintptr_t)(elems * sizes[i]) != 0) return false;
@@ -815,75 +682,202 @@ extern "C" int64_t advgrpo_sde_step_rescaled_workspace_bytes(int B, int C, int H
     return (int64_t)B * rs_blocks(H, W, 1) * sizeof(float);   // the one-token-per-lane grid: the larger of the two layouts
 }
 
-template <class Step>
-static int step_rescaled_fwd(const char* what, const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale, const void* x,
-                             int x_dtype, const float* sigma, const float* sigma_prev, int sigma_stride, float level,
-                             const float* sigma_max, int mode, const float* eps, uint64_t seed, uint64_t offset,
-                             const void* prev_sample, int prev_dtype, float* out_next_f32, void* out_next_cast, int out_cast_dtype,
-                             float* out_mean, float* out_log_prob, float* out_std, void* workspace, int B, int C, int H, int W,
-                             int patch_size, void* stream) {
-    if (rs_shape(what, v_dtype, x_dtype, B, C, H, W, patch_size, sigma_stride)) return -1;
-    ADVGRPO_CHECK(v_uncond && x && sigma && sigma_prev && out_log_prob && workspace, "%s: null argument", what);
-    ADVGRPO_CHECK((!std::is_same_v<Step, FlowStep>) || sigma_max, "%s: null sigma_max", what);
-    ADVGRPO_CHECK(mode >= 0 && mode <= 2, "%s: bad mode %d", what, mode);
-    ADVGRPO_CHECK(mode != ADVGRPO_SDE_EPS || eps, "%s: mode EPS needs eps", what);
-    ADVGRPO_CHECK(mode != ADVGRPO_SDE_REPLAY || prev_sample, "%s: mode REPLAY needs prev_sample", what);
-    ADVGRPO_CHECK(mode != ADVGRPO_SDE_REPLAY || prev_dtype == ADVGRPO_F32 || prev_dtype == ADVGRPO_BF16, "%s: bad prev_dtype %d", what,
-                  prev_dtype);
-    ADVGRPO_CHECK(!out_next_cast || mode == ADVGRPO_SDE_REPLAY || out_cast_dtype == ADVGRPO_F32 || out_cast_dtype == ADVGRPO_BF16,
-                  "%s: bad out_cast_dtype %d", what, out_cast_dtype);
-    const bool replay = mode == ADVGRPO_SDE_REPLAY;
-    const void* ptrs[] = {v_uncond, v_text, x, mode == ADVGRPO_SDE_EPS ? eps : nullptr, replay ? prev_sample : nullptr,
-                          replay ? nullptr : out_next_f32, replay ? nullptr : out_next_cast, out_mean};
-    const int sizes[] = {dtype_size(v_dtype), dtype_size(v_dtype), dtype_size(x_dtype), 4, dtype_size(prev_dtype), 4,
-                         dtype_size(out_cast_dtype), 4};
-    RsLaunch L;
-    if (rs_layout(what, ptrs, sizes, 8, C, H, W, &L)) return -1;
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(L.nb, B), dim3(QS_THREADS), 0, as_stream(stream), v_uncond, v_text, v_dtype, guidance_scale, x,
-                           x_dtype, sigma, sigma_prev, sigma_stride, level, sigma_max, mode, eps, seed, offset, prev_sample, prev_dtype,
-                           out_next_f32, out_next_cast, out_cast_dtype, out_mean, (float*)workspace, out_std, C, H, W);
-    };
-    if (L.pair) launch(sde_step_rescaled_kernel<Step, 2>);
-    else launch(sde_step_rescaled_kernel<Step, 1>);
-    ADVGRPO_LAUNCH_CHECK();
-    return step_finalize<Step>((const float*)workspace, L.nb, L.n, out_log_prob, B, sigma, sigma_prev, sigma_stride, B, level, sigma_max,
-                               stream);
+// The checks that come before the pointers.  The fan-out entries look at P, G first, so a bad n under them reports P as "B=".
+static int step_shape(const StepCall& c) {
+    if (c.shape == STEP_FAN) ADVGRPO_CHECK(c.B > 0 && c.G > 0, "%s: need P>0 and G>0 (P=%d G=%d)", c.what, c.B, c.G);
+    ADVGRPO_CHECK(c.v_dtype == ADVGRPO_F32 || c.v_dtype == ADVGRPO_BF16, "%s: bad v_dtype %d", c.common_what, c.v_dtype);
+    ADVGRPO_CHECK(c.x_dtype == ADVGRPO_F32 || c.x_dtype == ADVGRPO_BF16, "%s: bad x_dtype %d", c.common_what, c.x_dtype);
+    if (c.shape == STEP_TOKENS) return rs_shape(c.what, c.B, c.C, c.H, c.W, c.patch_size, c.sigma_stride);
+    ADVGRPO_CHECK(c.B > 0 && c.n > 0 && c.n % SDE_VEC == 0, "%s: need B>0 and n %% 8 == 0 (B=%d n=%lld)", c.common_what, c.B,
+                  (long long)c.n);
+    if (c.shape == STEP_FAN)
+        ADVGRPO_CHECK(c.B <= 65535 && fan_blocks(c.G) <= 65535 && (int64_t)c.B * c.G <= INT32_MAX, "%s: P=%d G=%d too large", c.what,
+                      c.B, c.G);
+    return 0;
 }
 
-// mean_ref == NULL: the policy-only backward (kl_weight, kl_out and workspace unused)
 template <class Step>
-static int step_rescaled_bwd(const char* what, const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
-                             const void* x, int x_dtype, const float* sigma, const float* sigma_prev, int sigma_stride, float level,
-                             const float* sigma_max, const void* prev_sample, int prev_dtype, const float* grad_log_prob,
-                             const float* mean_ref, float kl_weight, void* grad_v_uncond, void* grad_v_text, float* kl_out,
-                             void* workspace, int B, int C, int H, int W, int patch_size, void* stream) {
-    if (rs_shape(what, v_dtype, x_dtype, B, C, H, W, patch_size, sigma_stride)) return -1;
-    ADVGRPO_CHECK(v_uncond && x && sigma && sigma_prev && prev_sample && grad_log_prob && grad_v_uncond &&
-                      (!mean_ref || (kl_out && workspace)), "%s: null argument", what);
-    ADVGRPO_CHECK((!std::is_same_v<Step, FlowStep>) || sigma_max, "%s: null sigma_max", what);
-    ADVGRPO_CHECK(prev_dtype == ADVGRPO_F32 || prev_dtype == ADVGRPO_BF16, "%s: bad prev_dtype %d", what, prev_dtype);
-    ADVGRPO_CHECK(!v_text || grad_v_text, "%s: CFG needs grad_v_text", what);
-    const void* ptrs[] = {v_uncond, v_text, x, prev_sample, mean_ref, grad_v_uncond, v_text ? grad_v_text : nullptr};
-    const int sizes[] = {dtype_size(v_dtype), dtype_size(v_dtype), dtype_size(x_dtype), dtype_size(prev_dtype), 4, dtype_size(v_dtype),
-                         dtype_size(v_dtype)};
-    RsLaunch L;
-    if (rs_layout(what, ptrs, sizes, 7, C, H, W, &L)) return -1;
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(L.nb, B), dim3(QS_THREADS), 0, as_stream(stream), v_uncond, v_text, v_dtype, guidance_scale, x,
-                           x_dtype, sigma, sigma_prev, sigma_stride, level, sigma_max, prev_sample, prev_dtype, grad_log_prob,
-                           grad_v_uncond, grad_v_text, C, H, W, mean_ref, mean_ref ? kl_weight : 0.f, B,
-                           mean_ref ? (float*)workspace : (float*)nullptr);
+static int launch_forward(const StepCall& c, const StepGrid& g) {
+    auto launch = [&](auto kernel, dim3 grid, int threads, auto... shape) {
+        hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, as_stream(c.stream), c.v_uncond, c.v_text, c.v_dtype, c.guidance_scale, c.x,
+                           c.x_dtype, c.sigma, c.sigma_prev, c.sigma_stride, c.level, c.sigma_max, c.mode, c.eps, c.seed, c.offset,
+                           c.prev_sample, c.prev_dtype, c.out_next_f32, c.out_next_cast, c.out_cast_dtype, c.out_mean,
+                           (float*)c.workspace, c.out_std, shape...);
     };
-    if (L.pair) launch(sde_step_rescaled_bwd_kernel<Step, 2>);
-    else launch(sde_step_rescaled_bwd_kernel<Step, 1>);
+    if (c.shape == STEP_FLAT) launch(sde_step_kernel<Step>, dim3(g.nb, c.B), SDE_THREADS, g.n);
+    else if (c.shape == STEP_FAN) launch(sde_step_branch_kernel<Step>, dim3(g.nb, c.B, fan_blocks(c.G)), SDE_THREADS, c.B, c.G, g.n);
+    else if (g.pair) launch(sde_step_rescaled_kernel<Step, 2>, dim3(g.nb, c.B), QS_THREADS, c.C, c.H, c.W);
+    else launch(sde_step_rescaled_kernel<Step, 1>, dim3(g.nb, c.B), QS_THREADS, c.C, c.H, c.W);
     ADVGRPO_LAUNCH_CHECK();
-    if (mean_ref) {
-        hipLaunchKernelGGL(sde_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream), (const float*)workspace, L.nb, L.n,
-                           kl_out, B, 1.0f);
+    const int rows = c.B * c.G;                     // output row j takes the schedule row j % B
+    if (c.flow)
+        hipLaunchKernelGGL(flow_sde_finalize_kernel, dim3((rows + 63) / 64), dim3(64), 0, as_stream(c.stream),
+                           (const float*)c.workspace, g.nb, g.n, c.out_log_prob, rows, c.sigma, c.sigma_prev, c.sigma_stride, c.B, c.level,
+                           c.sigma_max);
+    else
+        hipLaunchKernelGGL(sde_finalize_kernel, dim3((rows + 63) / 64), dim3(64), 0, as_stream(c.stream), (const float*)c.workspace,
+                           g.nb, g.n, c.out_log_prob, rows, -1.0f);
+    ADVGRPO_LAUNCH_CHECK();
+    return 0;
+}
+
+static int step_forward(const StepCall& c) {
+    if (step_shape(c)) return -1;
+    ADVGRPO_CHECK(c.v_uncond && c.x && c.sigma && c.sigma_prev && c.out_log_prob && c.workspace, "%s: null argument", c.what);
+    ADVGRPO_CHECK(!c.flow || c.sigma_max, "%s: null sigma_max", c.what);
+    ADVGRPO_CHECK(c.mode >= 0 && c.mode <= 2, "%s: bad mode %d", c.what, c.mode);
+    ADVGRPO_CHECK(c.mode != ADVGRPO_SDE_EPS || c.eps, "%s: mode EPS needs eps", c.what);
+    const bool replay = c.mode == ADVGRPO_SDE_REPLAY;
+    ADVGRPO_CHECK(!replay || c.prev_sample, "%s: mode REPLAY needs prev_sample", c.what);
+    if (c.io_dtypes) {
+        ADVGRPO_CHECK(!replay || c.prev_dtype == ADVGRPO_F32 || c.prev_dtype == ADVGRPO_BF16, "%s: bad prev_dtype %d", c.what,
+                      c.prev_dtype);
+        ADVGRPO_CHECK(!c.out_next_cast || replay || c.out_cast_dtype == ADVGRPO_F32 || c.out_cast_dtype == ADVGRPO_BF16,
+                      "%s: bad out_cast_dtype %d", c.what, c.out_cast_dtype);
+    }
+    StepGrid g{false, sde_blocks(c.n), c.n};
+    if (c.shape == STEP_TOKENS) {
+        const void* ptrs[] = {c.v_uncond, c.v_text, c.x, c.mode == ADVGRPO_SDE_EPS ? c.eps : nullptr, replay ? c.prev_sample : nullptr,
+                              replay ? nullptr : c.out_next_f32, replay ? nullptr : c.out_next_cast, c.out_mean};
+        const int sizes[] = {dtype_size(c.v_dtype), dtype_size(c.v_dtype), dtype_size(c.x_dtype), 4, dtype_size(c.prev_dtype), 4,
+                             dtype_size(c.out_cast_dtype), 4};
+        if (rs_layout(c.what, ptrs, sizes, 8, c.C, c.H, c.W, &g)) return -1;
+    }
+    return c.flow ? launch_forward<FlowStep>(c, g) : launch_forward<CpsStep>(c, g);
+}
+
+template <class Step>
+static int launch_backward(const StepCall& c, const StepGrid& g) {
+    const float kl_weight = c.mean_ref ? c.kl_weight : 0.f;
+    float* kl_partial = c.mean_ref ? (float*)c.workspace : nullptr;
+    if (c.shape == STEP_TOKENS) {
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(g.nb, c.B), dim3(QS_THREADS), 0, as_stream(c.stream), c.v_uncond, c.v_text, c.v_dtype,
+                               c.guidance_scale, c.x, c.x_dtype, c.sigma, c.sigma_prev, c.sigma_stride, c.level, c.sigma_max, c.prev_sample,
+                               c.prev_dtype, c.grad_log_prob, c.grad_v_uncond, c.grad_v_text, c.C, c.H, c.W, c.mean_ref, kl_weight, c.B,
+                               kl_partial);
+        };
+        if (g.pair) launch(sde_step_rescaled_bwd_kernel<Step, 2>);
+        else launch(sde_step_rescaled_bwd_kernel<Step, 1>);
+    } else {
+        hipLaunchKernelGGL(sde_step_bwd_kernel<Step>, dim3(g.nb, c.B), dim3(SDE_THREADS), 0, as_stream(c.stream), c.v_uncond, c.v_text,
+                           c.v_dtype, c.guidance_scale, c.x, c.x_dtype, c.sigma, c.sigma_prev, c.sigma_stride, c.level, c.sigma_max,
+                           c.prev_sample, c.prev_dtype, c.grad_log_prob, c.grad_v_uncond, c.grad_v_text, g.n, c.mean_ref, kl_weight, c.B,
+                           kl_partial);
+    }
+    ADVGRPO_LAUNCH_CHECK();
+    if (c.mean_ref) {       // the per-sample KL values from the block partials
+        hipLaunchKernelGGL(sde_finalize_kernel, dim3((c.B + 63) / 64), dim3(64), 0, as_stream(c.stream), (const float*)c.workspace, g.nb,
+                           g.n, c.kl_out, c.B, 1.0f);
         ADVGRPO_LAUNCH_CHECK();
     }
     return 0;
+}
+
+static int step_backward(const StepCall& c) {
+    if (step_shape(c)) return -1;
+    ADVGRPO_CHECK(c.v_uncond && c.x && c.sigma && c.sigma_prev && c.prev_sample && c.grad_log_prob && c.grad_v_uncond &&
+                      (!c.need_mean_ref || c.mean_ref) && (!c.mean_ref || (c.kl_out && c.workspace)), "%s: null argument", c.what);
+    ADVGRPO_CHECK(!c.flow || c.sigma_max, "%s: null sigma_max", c.what);
+    if (c.io_dtypes) ADVGRPO_CHECK(c.prev_dtype == ADVGRPO_F32 || c.prev_dtype == ADVGRPO_BF16, "%s: bad prev_dtype %d", c.what, c.prev_dtype);
+    ADVGRPO_CHECK(!c.v_text || c.grad_v_text, "%s: CFG needs grad_v_text", c.what);
+    StepGrid g{false, sde_blocks(c.n), c.n};
+    if (c.shape == STEP_TOKENS) {
+        const void* ptrs[] = {c.v_uncond, c.v_text, c.x, c.prev_sample, c.mean_ref, c.grad_v_uncond, c.v_text ? c.grad_v_text : nullptr};
+        const int sizes[] = {dtype_size(c.v_dtype), dtype_size(c.v_dtype), dtype_size(c.x_dtype), dtype_size(c.prev_dtype), 4,
+                             dtype_size(c.v_dtype), dtype_size(c.v_dtype)};
+        if (rs_layout(c.what, ptrs, sizes, 7, c.C, c.H, c.W, &g)) return -1;
+    }
+    return c.flow ? launch_backward<FlowStep>(c, g) : launch_backward<CpsStep>(c, g);
+}
+
+extern "C" int advgrpo_sde_step(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                int sigma_stride, float sin_coeff, int mode, const float* eps, uint64_t seed,
+                                uint64_t offset, const void* prev_sample, int prev_dtype, float* out_next_f32,
+                                void* out_next_cast, int out_cast_dtype, float* out_mean, float* out_log_prob,
+                                float* out_std, void* workspace, int B, int64_t n, void* stream) {
+    STEP_CALL(c, "sde_step", false, sin_coeff, nullptr);
+    STEP_FORWARD(c);
+    return step_forward(c.flat(B, n));
+}
+
+extern "C" int advgrpo_sde_step_branch(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                       const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                       int sigma_stride, float sin_coeff, int mode, const float* eps, uint64_t seed,
+                                       uint64_t offset, const void* prev_sample, int prev_dtype, float* out_next_f32,
+                                       void* out_next_cast, int out_cast_dtype, float* out_mean, float* out_log_prob,
+                                       float* out_std, void* workspace, int P, int G, int64_t n, void* stream) {
+    STEP_CALL(c, "sde_step_branch", false, sin_coeff, nullptr);
+    STEP_FORWARD(c);
+    return step_forward(c.fan(P, G, n));
+}
+
+extern "C" int advgrpo_sde_step_bwd(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                    const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                    int sigma_stride, float sin_coeff, const void* prev_sample, int prev_dtype,
+                                    const float* grad_log_prob, void* grad_v_uncond, void* grad_v_text, int B,
+                                    int64_t n, void* stream) {
+    STEP_CALL(c, "sde_step_bwd", false, sin_coeff, nullptr);
+    STEP_BACKWARD(c);
+    return step_backward(c.flat(B, n));
+}
+
+extern "C" int advgrpo_sde_step_bwd_kl(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                       const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                       int sigma_stride, float sin_coeff, const void* prev_sample, int prev_dtype,
+                                       const float* grad_log_prob, const float* mean_ref, float kl_weight,
+                                       void* grad_v_uncond, void* grad_v_text, float* kl_out, void* workspace, int B,
+                                       int64_t n, void* stream) {
+    STEP_CALL(c, "sde_step_bwd_kl", false, sin_coeff, nullptr);
+    STEP_BACKWARD(c);
+    STEP_KL(c, true);
+    return step_backward(c.flat(B, n));
+}
+
+extern "C" int advgrpo_flow_sde_step(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                     const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                     int sigma_stride, float noise_level, const float* sigma_max, int mode, const float* eps,
+                                     uint64_t seed, uint64_t offset, const void* prev_sample, int prev_dtype,
+                                     float* out_next_f32, void* out_next_cast, int out_cast_dtype, float* out_mean,
+                                     float* out_log_prob, float* out_std, void* workspace, int B, int64_t n, void* stream) {
+    STEP_CALL(c, "flow_sde_step", true, noise_level, sigma_max);
+    STEP_FORWARD(c);
+    return step_forward(c.flat(B, n));
+}
+
+extern "C" int advgrpo_flow_sde_step_branch(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                            const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                            int sigma_stride, float noise_level, const float* sigma_max, int mode,
+                                            const float* eps, uint64_t seed, uint64_t offset, const void* prev_sample,
+                                            int prev_dtype, float* out_next_f32, void* out_next_cast, int out_cast_dtype,
+                                            float* out_mean, float* out_log_prob, float* out_std, void* workspace, int P, int G,
+                                            int64_t n, void* stream) {
+    STEP_CALL(c, "flow_sde_step_branch", true, noise_level, sigma_max);
+    STEP_FORWARD(c);
+    return step_forward(c.fan(P, G, n));
+}
+
+extern "C" int advgrpo_flow_sde_step_bwd(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                         const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                         int sigma_stride, float noise_level, const float* sigma_max, const void* prev_sample,
+                                         int prev_dtype, const float* grad_log_prob, void* grad_v_uncond, void* grad_v_text,
+                                         int B, int64_t n, void* stream) {
+    STEP_CALL(c, "flow_sde_step_bwd", true, noise_level, sigma_max);
+    STEP_BACKWARD(c);
+    return step_backward(c.flat(B, n));
+}
+
+extern "C" int advgrpo_flow_sde_step_bwd_kl(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
+                                            const void* x, int x_dtype, const float* sigma, const float* sigma_prev,
+                                            int sigma_stride, float noise_level, const float* sigma_max,
+                                            const void* prev_sample, int prev_dtype, const float* grad_log_prob,
+                                            const float* mean_ref, float kl_weight, void* grad_v_uncond, void* grad_v_text,
+                                            float* kl_out, void* workspace, int B, int64_t n, void* stream) {
+    STEP_CALL(c, "flow_sde_step_bwd_kl", true, noise_level, sigma_max);
+    STEP_BACKWARD(c);
+    STEP_KL(c, true);
+    return step_backward(c.flat(B, n));
 }
 
 extern "C" int advgrpo_sde_step_rescaled(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale, const void* x,
@@ -892,10 +886,9 @@ extern "C" int advgrpo_sde_step_rescaled(const void* v_uncond, const void* v_tex
                                          int prev_dtype, float* out_next_f32, void* out_next_cast, int out_cast_dtype, float* out_mean,
                                          float* out_log_prob, float* out_std, void* workspace, int B, int C, int H, int W,
                                          int patch_size, void* stream) {
-    return step_rescaled_fwd<CpsStep>("sde_step_rescaled", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev,
-                                      sigma_stride, sin_coeff, nullptr, mode, eps, seed, offset, prev_sample, prev_dtype, out_next_f32,
-                                      out_next_cast, out_cast_dtype, out_mean, out_log_prob, out_std, workspace, B, C, H, W, patch_size,
-                                      stream);
+    STEP_CALL(c, "sde_step_rescaled", false, sin_coeff, nullptr);
+    STEP_FORWARD(c);
+    return step_forward(c.tokens(B, C, H, W, patch_size));
 }
 
 extern "C" int advgrpo_flow_sde_step_rescaled(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale, const void* x,
@@ -905,10 +898,9 @@ extern "C" int advgrpo_flow_sde_step_rescaled(const void* v_uncond, const void* 
                                               void* out_next_cast, int out_cast_dtype, float* out_mean, float* out_log_prob,
                                               float* out_std, void* workspace, int B, int C, int H, int W, int patch_size,
                                               void* stream) {
-    return step_rescaled_fwd<FlowStep>("flow_sde_step_rescaled", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev,
-                                       sigma_stride, noise_level, sigma_max, mode, eps, seed, offset, prev_sample, prev_dtype,
-                                       out_next_f32, out_next_cast, out_cast_dtype, out_mean, out_log_prob, out_std, workspace, B, C, H,
-                                       W, patch_size, stream);
+    STEP_CALL(c, "flow_sde_step_rescaled", true, noise_level, sigma_max);
+    STEP_FORWARD(c);
+    return step_forward(c.tokens(B, C, H, W, patch_size));
 }
 
 extern "C" int advgrpo_sde_step_rescaled_bwd(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale, const void* x,
@@ -917,9 +909,10 @@ extern "C" int advgrpo_sde_step_rescaled_bwd(const void* v_uncond, const void* v
                                              const float* mean_ref, float kl_weight, void* grad_v_uncond, void* grad_v_text,
                                              float* kl_out, void* workspace, int B, int C, int H, int W, int patch_size,
                                              void* stream) {
-    return step_rescaled_bwd<CpsStep>("sde_step_rescaled_bwd", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma, sigma_prev,
-                                      sigma_stride, sin_coeff, nullptr, prev_sample, prev_dtype, grad_log_prob, mean_ref, kl_weight,
-                                      grad_v_uncond, grad_v_text, kl_out, workspace, B, C, H, W, patch_size, stream);
+    STEP_CALL(c, "sde_step_rescaled_bwd", false, sin_coeff, nullptr);
+    STEP_BACKWARD(c);
+    STEP_KL(c, false);
+    return step_backward(c.tokens(B, C, H, W, patch_size));
 }
 
 extern "C" int advgrpo_flow_sde_step_rescaled_bwd(const void* v_uncond, const void* v_text, int v_dtype, float guidance_scale,
@@ -929,10 +922,10 @@ extern "C" int advgrpo_flow_sde_step_rescaled_bwd(const void* v_uncond, const vo
                                                   const float* mean_ref, float kl_weight, void* grad_v_uncond, void* grad_v_text,
                                                   float* kl_out, void* workspace, int B, int C, int H, int W, int patch_size,
                                                   void* stream) {
-    return step_rescaled_bwd<FlowStep>("flow_sde_step_rescaled_bwd", v_uncond, v_text, v_dtype, guidance_scale, x, x_dtype, sigma,
-                                       sigma_prev, sigma_stride, noise_level, sigma_max, prev_sample, prev_dtype, grad_log_prob,
-                                       mean_ref, kl_weight, grad_v_uncond, grad_v_text, kl_out, workspace, B, C, H, W, patch_size,
-                                       stream);
+    STEP_CALL(c, "flow_sde_step_rescaled_bwd", true, noise_level, sigma_max);
+    STEP_BACKWARD(c);
+    STEP_KL(c, false);
+    return step_backward(c.tokens(B, C, H, W, patch_size));
 }
 
 extern "C" int advgrpo_randn(void* out, int out_dtype, int64_t n, uint64_t seed, uint64_t offset, void* stream) {

@@ -20,6 +20,7 @@ from .. import _lib
 
 
 SDE_TYPES = ("cps", "sde")
+_ENTRY = {"cps": "advgrpo_sde_step", "sde": "advgrpo_flow_sde_step"}   # + "", _branch, _bwd, _bwd_kl, _rescaled, _rescaled_bwd
 
 
 def _sigma_tables(scheduler, timestep, B, device):
@@ -44,6 +45,14 @@ def rescaled_prediction(v_uncond, v_text, guidance_scale):
     cond_norm = torch.norm(pos, dim=-1, keepdim=True)
     noise_norm = torch.norm(comb, dim=-1, keepdim=True)
     return _unpack(comb * (cond_norm / noise_norm), C, H, W).contiguous()
+
+
+def _step_head(v_uncond, v_text, guidance_scale, sample, sig, sigp, stride, sde_type, noise_level, tab, ptr=_lib.ptr):
+    """What all twelve step entries start with: v_uncond .. sigma_stride, then the level -- sin(noise_level pi / 2) for Flow-CPS;
+    noise_level and a device pointer to sigma_max = tab[1] (SDE:46) for Flow-SDE."""
+    level = (float(noise_level), ptr(tab[1:2])) if sde_type == "sde" else (float(math.sin(noise_level * math.pi / 2)),)
+    return (ptr(v_uncond), ptr(v_text), _lib.dtype_code(v_uncond.dtype), float(guidance_scale), ptr(sample),
+            _lib.dtype_code(sample.dtype), ptr(sig), ptr(sigp), stride, *level)
 
 
 def sde_step_cfg(scheduler, v_uncond, v_text, guidance_scale, timestep, sample, noise_level=0.7,
@@ -80,7 +89,6 @@ def sde_step_cfg(scheduler, v_uncond, v_text, guidance_scale, timestep, sample, 
         return sde_step_cfg(scheduler, rescaled_prediction(v_uncond, v_text, guidance_scale), None, 1.0, timestep, sample, noise_level,
                             prev_sample=prev_sample, noise=noise, seed=seed, offset=offset, out_dtype=out_dtype, want_mean=want_mean,
                             step_index=step_index, sigmas=sigmas, sde_type=sde_type)
-    flow = sde_type == "sde"
     lib = _lib.load()
     P = sample.shape[0]
     B = P if copies is None else P * int(copies)
@@ -121,21 +129,40 @@ def sde_step_cfg(scheduler, v_uncond, v_text, guidance_scale, timestep, sample, 
         shape = ((B,) if copies is None else (P, int(copies))) + (n,)
         ws_bytes = lib.advgrpo_sde_step_workspace_bytes(B, n)
     ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device=dev)
-    if flow:                                                       # noise_level and a device pointer to sigma_max = sigmas[1] (SDE:46)
-        entry = lib.advgrpo_flow_sde_step_rescaled if rescale else lib.advgrpo_flow_sde_step if copies is None else lib.advgrpo_flow_sde_step_branch
-        level = (float(noise_level), _lib.ptr(tab[1:2]))
-    else:
-        entry = lib.advgrpo_sde_step_rescaled if rescale else lib.advgrpo_sde_step if copies is None else lib.advgrpo_sde_step_branch
-        level = (float(math.sin(noise_level * math.pi / 2)),)
-    _lib.check(entry(
-        _lib.ptr(v_uncond), _lib.ptr(v_text), _lib.dtype_code(v_uncond.dtype), float(guidance_scale),
-        _lib.ptr(sample), _lib.dtype_code(sample.dtype), _lib.ptr(sig), _lib.ptr(sigp), stride,
-        *level, mode, _lib.ptr(noise) if mode == _lib.SDE_EPS else None,
+    _lib.check(getattr(lib, _ENTRY[sde_type] + ("_rescaled" if rescale else "" if copies is None else "_branch"))(
+        *_step_head(v_uncond, v_text, guidance_scale, sample, sig, sigp, stride, sde_type, noise_level, tab),
+        mode, _lib.ptr(noise) if mode == _lib.SDE_EPS else None,
         int(seed or 0), int(offset), _lib.ptr(prev_sample) if replay else None,
         _lib.dtype_code(prev_sample.dtype) if replay else 0, _lib.ptr(nxt), _lib.ptr(cast),
         _lib.dtype_code(cast.dtype) if cast is not None else 0, _lib.ptr(mean), _lib.ptr(lp), _lib.ptr(std),
         _lib.ptr(ws), *shape, _lib.stream_ptr()))
     return nxt, cast, lp, mean, std.view(-1, *([1] * (sample.dim() - 1)))
+
+
+def sde_step_cfg_bwd(scheduler, v_uncond, v_text, guidance_scale, sample, noise_level, prev_sample, grad_log_prob, step_index,
+                     mean_ref=None, kl_weight=0.0, sde_type="cps", cfg_rescale=False):
+    """Backward of the replay-mode ``sde_step_cfg`` at scheduler index `step_index`: d loss / d log_prob [B] in, (d loss / d v_uncond,
+    d loss / d v_text, kl) out, the gradients in the predictions' dtype.  mean_ref (the same step's mean under the reference
+    transformer) adds kl_weight * mean_b mean_elem (mean - mean_ref)^2 to the loss and returns its per-sample values in `kl` [B];
+    without it kl is None.  The entry follows (sde_type, cfg_rescale, mean_ref is None): advgrpo_{,flow_}sde_step_bwd{,_kl}, or the one
+    advgrpo_{,flow_}sde_step_rescaled_bwd whose mean_ref is nullable."""
+    lib, tab, B, dev = _lib.load(), scheduler.sigmas, sample.shape[0], sample.device
+    gu, gt = torch.empty_like(v_uncond), torch.empty_like(v_text)
+    shape = (*sample.shape, 2) if cfg_rescale else (B, sample[0].numel())          # (B, C, H, W, patch_size) in place of (B, n)
+    kl = ws = None
+    if mean_ref is not None:
+        query = lib.advgrpo_sde_step_rescaled_workspace_bytes if cfg_rescale else lib.advgrpo_sde_step_workspace_bytes
+        kl = torch.empty(B, dtype=torch.float32, device=dev)
+        ws = torch.empty(max(1, query(*shape) // 4), dtype=torch.float32, device=dev)
+    suffix = "_rescaled_bwd" if cfg_rescale else "_bwd" if mean_ref is None else "_bwd_kl"
+    ptr = lambda t: None if t is None else t.data_ptr()            # unchecked, as the G-step always passed its own fresh tensors
+    kl_in, kl_out = ((), ()) if suffix == "_bwd" else ((ptr(mean_ref), float(kl_weight)), (ptr(kl), ptr(ws)))
+    _lib.check(getattr(lib, _ENTRY[sde_type] + suffix)(
+        *_step_head(v_uncond, v_text, guidance_scale, sample, tab[step_index:step_index + 1], tab[step_index + 1:step_index + 2], 0,
+                    sde_type, noise_level, tab, ptr),
+        ptr(prev_sample), _lib.dtype_code(prev_sample.dtype), ptr(grad_log_prob), *kl_in, ptr(gu), ptr(gt), *kl_out, *shape,
+        _lib.stream_ptr()))
+    return gu, gt, kl
 
 
 def _step_with_logprob(sde_type, scheduler, model_output, timestep, sample, noise_level, prev_sample, generator, noise):

@@ -4,12 +4,10 @@ Mirror of the inner training loop body, scripts/train_sd3_fast_pickscore.py:1102
 beta > 0 adds the KL term of TP:1105-1108,1126-1130 against the adapter-free transformer): compute_log_prob (TP:233-267) = transformer on the CFG batch + CFG combine + SDE step in replay mode;
 loss block TP:1111-1130; accelerator.backward(loss) TP:1165.  The backward is explicit:
 d loss/d log_prob (grpo_loss kernel) -> d/d v_uncond, d/d v_text (sde_step_bwd kernel) -> MMDiT backward."""
-import math
-
 import torch
 
-from . import _lib, losses
-from .diffusers_patch.sd3_sde_with_logprob import sde_step_cfg
+from . import losses
+from .diffusers_patch.sd3_sde_with_logprob import sde_step_cfg, sde_step_cfg_bwd
 
 
 @torch.no_grad()
@@ -30,9 +28,7 @@ def micro_step(model, scheduler, sample, j, embeds, pooled_embeds, old_log_prob,
     embeds_mask: the prompt mask of `embeds` ([2 G, Nt], same row order; Qwen-Image), handed to forward_train as encoder_hidden_states_mask
     and to the reference forward; None: nothing is passed.
     cfg_rescale: the rollout combined its predictions with Qwen-Image's norm-rescaled true CFG (sde_step_cfg(cfg_rescale=True)): the
-    replay forward and the reference mean do too, and the backward is advgrpo_sde_step_rescaled_bwd / advgrpo_flow_sde_step_rescaled_bwd,
-    whose gradient passes through the norm ratio (one entry for beta == 0 and beta > 0)."""
-    lib = _lib.load()
+    replay forward, the reference mean and the backward (sde_step_cfg_bwd, whose gradient then passes through the norm ratio) do too."""
     x = sample["latents"][:, j].contiguous()
     nxt = sample["next_latents"][:, j].contiguous()
     ts = sample["timesteps"][:, j]
@@ -54,33 +50,8 @@ def micro_step(model, scheduler, sample, j, embeds, pooled_embeds, old_log_prob,
     scal, dlp = losses.grpo_loss(log_prob, old_log_prob, advantages, adv_clip_max, clip_range)
     if loss_scale != 1.0:
         dlp = dlp * loss_scale
-    gu, gt = torch.empty_like(vu), torch.empty_like(vt)
-    n = vu[0].numel()
-    sig, sigp = scheduler.sigmas[step_index:step_index + 1], scheduler.sigmas[step_index + 1:step_index + 2]
-    if sde_type == "sde":                                # noise_level and a device pointer to sigma_max = sigmas[1] (SDE:46)
-        bwd, bwd_kl = lib.advgrpo_flow_sde_step_bwd, lib.advgrpo_flow_sde_step_bwd_kl
-        level = (float(noise_level), scheduler.sigmas[1:2].data_ptr())
-    else:
-        bwd, bwd_kl = lib.advgrpo_sde_step_bwd, lib.advgrpo_sde_step_bwd_kl
-        level = (float(math.sin(noise_level * math.pi / 2)),)
-    common = (vu.data_ptr(), vt.data_ptr(), _lib.dtype_code(vu.dtype), float(guidance_scale), x.data_ptr(),
-              _lib.dtype_code(x.dtype), sig.data_ptr(), sigp.data_ptr(), 0, *level,
-              nxt.data_ptr(), _lib.dtype_code(nxt.dtype), dlp.data_ptr())
-    kl = None
-    if cfg_rescale:
-        if mean_ref is not None:
-            kl = torch.empty(G, dtype=torch.float32, device=x.device)
-            ws = torch.empty(max(1, lib.advgrpo_sde_step_rescaled_workspace_bytes(*x.shape, 2) // 4), dtype=torch.float32, device=x.device)
-        bwd = lib.advgrpo_flow_sde_step_rescaled_bwd if sde_type == "sde" else lib.advgrpo_sde_step_rescaled_bwd
-        _lib.check(bwd(*common, _lib.ptr(mean_ref), float(beta) * float(loss_scale), gu.data_ptr(), gt.data_ptr(), _lib.ptr(kl),
-                       _lib.ptr(ws) if kl is not None else None, *x.shape, 2, _lib.stream_ptr()))
-    elif mean_ref is None:
-        _lib.check(bwd(*common, gu.data_ptr(), gt.data_ptr(), G, n, _lib.stream_ptr()))
-    else:
-        kl = torch.empty(G, dtype=torch.float32, device=x.device)
-        ws = torch.empty(max(1, lib.advgrpo_sde_step_workspace_bytes(G, n) // 4), dtype=torch.float32, device=x.device)
-        _lib.check(bwd_kl(*common, mean_ref.data_ptr(), float(beta) * float(loss_scale), gu.data_ptr(),
-                          gt.data_ptr(), kl.data_ptr(), ws.data_ptr(), G, n, _lib.stream_ptr()))
+    gu, gt, kl = sde_step_cfg_bwd(scheduler, vu, vt, guidance_scale, x, noise_level, nxt, dlp, step_index, mean_ref=mean_ref,
+                                  kl_weight=float(beta) * float(loss_scale), sde_type=sde_type, cfg_rescale=cfg_rescale)
     model.backward(ctx, torch.cat([gu, gt]))
     info = {"log_prob": log_prob, "scalars": scal, **{k: scal[i] for i, k in enumerate(losses.INFO_KEYS)}}
     if kl is not None:                                   # TP:1126-1130,1158-1160
